@@ -7,6 +7,7 @@ A "step" = zero_grad + forward + backward + (gradient all-reduce if N>1) + Adam,
 global_step >= 2000 (training wheel off: every gradient path live, nothing skipped).
 
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR     # + what the last timed step computed, as DIR/<name>.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 """
@@ -278,6 +279,33 @@ def attach_pmc_traffic(kernels, B, image, dtype):
             rec["traffic_source"] = rel
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, model, last, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what the last timed step handed its caller -- the loss terms, the forward's recon / z_where / z_pres, the parameter
+    gradient of its backward and the parameters after its Adam update -- as <out_dir>/<name>.npy in float32.  Smallest first; an array that
+    does not fit the rest of the budget is cut to a fixed, seeded sample of its leading axis (sorted rows; the same shapes give the same
+    rows), so two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = dict(loss_terms=model.loss_terms(), z_pres=last["z_pres"], z_where=last["z_where"], grad=model.flat_gradients(),
+                  params=model.flat_parameters(), recon=last["recon"])
+    os.makedirs(out_dir, exist_ok=True)
+    left = budget
+    for name, t in sorted(arrays.items(), key=lambda kv: kv[1].numel()):
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > left:
+            row = a.nbytes // a.shape[0]
+            keep = left // row
+            if keep < 1:
+                raise SystemExit("bench.py: --dump-outputs: %s does not fit the %d-byte budget" % (name, budget))
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
+
+
 def config3_record(dev, args, strides):
     """BASELINE configs[3]: 256x256 scenes, 32x32 grid, batch 64 (same N = B*G*G as configs[1]) -- ms per step and the chain / renderer
     roofline fractions, bounded to a few seconds."""
@@ -350,18 +378,23 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--global-step", type=int, default=2000, help="global_step of the first timed step (count-prior / wheel schedules)")
-    ap.add_argument("--sweep", action="store_true", help="(kept for compatibility: the sweep is part of the default single-GPU line)")
-    ap.add_argument("--no-sweep", action="store_true",
-                    help="skip BASELINE configs[4]: after the main measurement, the step at global_step in {0,2000,4000,6000,7000,8000,10000}")
+    ap.add_argument("--sweep", action="store_true",
+                    help="add BASELINE configs[4] to the single-GPU line: after the main measurement, the step at global_step in "
+                         "{0,2000,4000,6000,7000,8000,10000}, at 1 / 3 / 6 / 11 objects and at nine presence / size states (20 points, ~10 KB of JSON)")
+    ap.add_argument("--no-sweep", action="store_true", help="(kept for compatibility: the sweep runs only with --sweep)")
     ap.add_argument("--sweep-steps", type=int, default=10)
     ap.add_argument("--no-config3", action="store_true",
                     help="skip the bounded BASELINE configs[3] sub-record (256x256, 32x32 grid, batch 64) of the default single-GPU line")
     ap.add_argument("--config3-steps", type=int, default=20)
     ap.add_argument("--dense-input", action="store_true", help="diagnostic: uniform-noise images (no zero pixels) instead of scattered digits; "
                                                                 "config.workload says so")
-    ap.add_argument("--repeat", type=int, default=3, help="repeat the K-step timed region this many times; the MEDIAN repeat is reported")
+    ap.add_argument("--repeat", type=int, default=1, help="repeat the K-step timed region this many times (K x repeat timed steps); the MEDIAN "
+                                                          "repeat is reported")
     ap.add_argument("--prof-every", type=int, default=4, help="record the per-kernel HIP event pairs on every n-th timed step")
     ap.add_argument("--prof-mask", type=lambda v: int(v, 0), default=-1, help="bit mask of the engine's event-pair slots to record (-1 = all)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (loss terms, recon, z_where, z_pres, the parameter "
+                         "gradient and the updated parameters) as DIR/<name>.npy, float32, at most 64 MB in all (rank 0)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -414,6 +447,7 @@ def main():
     def step():
         opt.zero_grad()
         loss, recon, z_where, z_pres = model(x, gstep[0])
+        last["recon"] = recon
         last["z_pres"] = z_pres
         last["z_where"] = z_where
         last["loss"] = loss
@@ -432,7 +466,7 @@ def main():
     L.check(lib.spair_prof_select(ctypes.c_ulonglong(args.prof_mask & 0xFFFFFFFFFFFFFFFF)), "prof_select")
     L.check(lib.spair_prof_enable(1), "prof_enable")
     lib.spair_prof_enable(0)
-    # EXACTLY K steps bracketed by barrier + synchronize on both sides; the bracket is repeated `--repeat` times (default 3) and the
+    # EXACTLY K steps bracketed by barrier + synchronize on both sides; with `--repeat R` (default 1) the bracket runs R times and the
     # MEDIAN repeat is the line's ms_per_step / value (`ms_per_step_repeats` lists all of them, `ms_per_step_min` the fastest): one
     # host-side hiccup (allocator, Python GC, a cold page) in a 0.1 s region does not decide the line, and neither does the luckiest
     # repeat.  Per-kernel event pairs are sampled at the same cadence in EVERY repeat, so the reported repeat carries them too.
@@ -459,6 +493,8 @@ def main():
         tt = torch.tensor(rep_dt, device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)          # MAX over ranks, per repeat
         rep_dt = [float(v) for v in tt.tolist()]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last)    # before anything else runs a step on this model
     srt = sorted(rep_dt)
     dt = srt[len(srt) // 2] if len(srt) % 2 else 0.5 * (srt[len(srt) // 2 - 1] + srt[len(srt) // 2])     # the median repeat
     terms = model.loss_terms().clone()
@@ -522,7 +558,7 @@ def main():
     if ddp_rec is not None:
         out["ddp"] = ddp_rec
     default_workload = args.image == 128 and B == 256 and d.G == 16 and args.dtype == "bf16" and not args.dense_input
-    if world == 1 and not args.no_sweep and (args.sweep or default_workload):
+    if world == 1 and args.sweep:
         # BASELINE configs[4] on one GPU: "z_pres discovery-prior curriculum sweep (max_objects 1 -> 11) ... sequential compositing kernel
         # under varying active-cell density".  Three axes, every point from the same model and optimizer state:
         #   schedule : global_step of the count-prior / training-wheel schedules (config.py:65-69, models.py:186-188), the bench batch;

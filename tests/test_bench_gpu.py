@@ -1,4 +1,4 @@
-"""The driver's command, `python bench.py` with its default sub-records, end to end on the GPU box (shortened loops): ONE JSON line with the
+"""The driver's command, `python bench.py` with its sub-records (configs[4] sweep on request), end to end on the GPU box (shortened loops): ONE JSON line with the
 contract's keys, the roofline / kernels objects, the configs[4] sweep, the configs[3] sub-record and the fused-stage K4 entry."""
 import json
 import os
@@ -12,8 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_default_bench_line_has_every_sub_record():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--sweep-steps", "1", "--config3-steps", "2",
-           "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--sweep", "--sweep-steps", "1",
+           "--config3-steps", "2", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -48,3 +48,32 @@ def test_default_bench_line_has_every_sub_record():
     c3 = rec["config3"]
     assert "configs[3]" in c3["workload"] and c3["ms_per_step"] > 0 and "stn_fwd" in c3["kernels"]
     assert c3["finite"] is True and c3["chain_status"] == 0
+
+
+def test_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs: K timed steps exactly, then the last step's outputs as float32 .npy files within the 64 MB budget, the same from
+    run to run of the same arguments (inputs, weights and noise are seeded and the step repeats to the bit: test_round3_gpu)."""
+    import numpy as np
+    recs, dumps = [], []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "32", "--no-config3",
+               "--no-cpu-baseline", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        recs.append(json.loads(lines[0]))
+        dumps.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    for rec in recs:
+        assert rec["steps"] == 3 and rec["repeat"] == 1 and rec["ms_per_step"] > 0 and "sweep" not in rec
+    a, b = dumps
+    assert set(a) == {"loss_terms", "recon", "z_where", "z_pres", "grad", "params"}
+    assert sum(v.nbytes for v in a.values()) <= 64 * 10 ** 6
+    assert a["recon"].shape == (32, 1, 128, 128) and a["z_where"].shape == (32, 4, 16, 16) and a["z_pres"].shape == (32, 1, 16, 16)
+    for k in a:
+        assert a[k].dtype == np.float32 and a[k].shape == b[k].shape and np.isfinite(a[k]).all(), k
+    # the dumped total is the step's loss: it matches the line's ELBO, and the second run reproduces the first
+    assert abs(float(a["loss_terms"][0]) - recs[0]["elbo"]) <= 1e-6 * abs(recs[0]["elbo"])
+    for k in a:
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-4, atol=1e-5, err_msg=k)

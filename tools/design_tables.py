@@ -8,7 +8,7 @@ files they quote.
 Inputs (all under profiles/, produced on the GPU box by tools/profile_set.sh <tag> and `python bench.py`):
   <tag>_kernel_stats.csv   rocprofv3 --kernel-trace --stats of `bench.py --no-sweep --no-config3` (average duration per kernel name)
   <tag>_step_timeline.txt  the last traced step, launch by launch (tools/step_trace.py): separates the k_tn_ring launches that share a name
-  <tag>_bench.json         the default `python bench.py` line (event times, sweep, config3, step breakdown)
+  <tag>_bench.json         the `python bench.py --sweep` line (event times, sweep, config3, step breakdown)
   <tag>_pmc_traffic.txt    HBM bytes per launch (FETCH_SIZE / WRITE_SIZE passes, tools/pmc_summary.py)
   <tag>_sq_counters.txt    SQ counter ratios (tools/sq_summary.py);  <tag>_l2_requests.txt  L1 -> L2 requests (tools/l2_summary.py)
   <tag>_gputest.txt        tail of `pytest tests -m gpu` at that state (optional: the test count)
