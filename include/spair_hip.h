@@ -117,6 +117,22 @@ int spair_backward_ev(const SpairDims* d, const SpairStep* st, const float* para
                       const float* eps_box, const float* eps_attr, const float* eps_depth, const float* u_pres,
                       void* workspace, const float* grad_loss, float* grads, void* stream,
                       void* ev_decoder, void* ev_cells, void* ev_backbone);
+/* Differentiable outputs (the reference returns recon, z_where and z_pres as autograd tensors, models.py:35-131, so a user term on any of
+ * them trains through the model).  spair_forward_out is spair_forward that also keeps inv_den [B][I][I] (1/D of the renderer's composite per
+ * pixel; NULL = not kept).  spair_backward_out is spair_backward_ev that also folds the adjoints of the three outputs into the reverse pass:
+ * grad_recon [B,C,I,I] (needs the inv_den of the same forward, else SPAIR_ERR_SHAPE), grad_z_where [B,4,G,G], grad_z_pres [B,1,G,G]; any of
+ * them may be NULL, and one that is NULL launches nothing (all three NULL = spair_backward_ev, kernel for kernel).  grad_loss may point at a
+ * zero for a backward through the outputs alone.  aux_scratch: 2*B*C*I*I + 1 floats, only touched with grad_recon (the workspace keeps
+ * what the forward saved, so a second backward through the same forward is unaffected).  Element for element, no atomics: deterministic. */
+int spair_forward_out(const SpairDims* d, const SpairStep* st, const float* params, const float* x,
+                      const float* eps_box, const float* eps_attr, const float* eps_depth, const float* u_pres,
+                      void* workspace, float* loss_out, float* recon, float* z_where, float* z_pres, void* stream, float* inv_den);
+int spair_backward_out(const SpairDims* d, const SpairStep* st, const float* params, const float* x,
+                       const float* eps_box, const float* eps_attr, const float* eps_depth, const float* u_pres,
+                       void* workspace, const float* grad_loss, float* grads, void* stream,
+                       void* ev_decoder, void* ev_cells, void* ev_backbone,
+                       const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
+                       float* aux_scratch);
 /* torch.optim.Adam(lr) defaults (train.py:44) on flat buffers, one launch. */
 int spair_adam(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                float beta1, float beta2, float eps, int step, void* stream);

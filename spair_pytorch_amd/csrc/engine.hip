@@ -22,16 +22,20 @@ int stn_glimpse_fwd(const float* x, const float* nbox, int B, float* out, int ld
 int stn_glimpse_bwd(const float* x, const float* nbox, int B, const float* dgl, int ld, float* dnbox, int r0, int R, int C, int I, int P, int ac, int px16, hipStream_t s);
 int render_sprite_act(float* S, int ld, int N, int per, int CH, float obj_scale, float alpha_scale, float alpha_bias, hipStream_t s);
 int render_num_blocks(int B, int I);
-int render_fwd(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* x, float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int ac, int s_bf16, hipStream_t s);
+int render_fwd(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* x, float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int ac, int s_bf16, float* inv_den, hipStream_t s);
 int render_prep(const float* nbox, const float* pres, const float* depth, int ld_pd, void* rec, int B, int HW, int I, int P, int ac, hipStream_t s);
-int render_fwd_mma(const void* S16, int ld_s, const void* rec, const float* x, float* recon, float* aux, float* bce_partial, int B, int HW, int I, int P, int ac, hipStream_t s);
+int render_fwd_mma(const void* S16, int ld_s, const void* rec, const float* x, float* recon, float* aux, float* bce_partial, int B, int HW, int I, int P, int ac, float* inv_den, hipStream_t s);
 int render_bwd(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* aux, const float* gloss, float* dlogits, float* dnbox, float* dpres, float* ddepth, int ld_g, int B, int HW, int C, int I, int P, int ac, float obj_scale, float alpha_scale, int g_bf16, int s_bf16, const void* rec, hipStream_t s);
 int render_prep_supported(int HW, int I, int P, int ac);
 int render_fwd_c(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* x, float* recon,
-                 float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int ac, hipStream_t s);
+                 float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int ac, float* inv_den, hipStream_t s);
 int render_bwd_c(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* aux,
                  const float* gloss, float* dlogits, float* dnbox, float* dpres, float* ddepth, int ld_g, int B, int HW, int C, int I, int P,
                  int ac, float obj_scale, float alpha_scale, hipStream_t s);
+int outgrad_recon_fold(const float* aux, const float* gloss, const float* grad_recon, const float* inv_den, float* aux_ext, float* one, int B,
+                       int C, int I, hipStream_t s);
+int outgrad_rows_fold(const int* cell_h, const int* cell_w, int B, int G, const float* g_z_where, const float* g_z_pres, float* g_nbox_r,
+                      float* g_pres_r, hipStream_t s);
 int loss_count_kl(const CellLayout& L, const CellBufs& P, float prior_prob, float* klp, hipStream_t s);
 int loss_gauss_kl_blocks(const CellLayout& L);
 int loss_gauss_kl(const CellLayout& L, const CellBufs& P, const CellHyper& H, float* partial, hipStream_t s);
@@ -1131,6 +1135,12 @@ static int cells_fwd(Ctx& c) {
 extern "C" int spair_forward(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
                              const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace, float* loss_out,
                              float* recon, float* z_where, float* z_pres, void* stream) {
+    return spair_forward_out(d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, loss_out, recon, z_where, z_pres, stream, nullptr);
+}
+
+extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
+                                 const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace, float* loss_out,
+                                 float* recon, float* z_where, float* z_pres, void* stream, float* inv_den) {
     Ctx c;
     TRY(make_ctx(c, d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, stream));
     if (!loss_out || !recon || !z_where || !z_pres || !eps_box || !eps_attr || !eps_depth || !u_pres) return SPAIR_ERR_SHAPE;
@@ -1233,14 +1243,14 @@ extern "C" int spair_forward(const SpairDims* d, const SpairStep* st, const floa
         int rc = SPAIR_ERR_UNSUPPORTED;
         if (rc_prep == SPAIR_OK) {
             rc = render_fwd_mma(c.w.S, c.w.ld_s, c.w.rrec, x, recon, st->train ? c.w.aux : nullptr, c.w.bce_partial, d->B, L.HW, d->I,
-                                d->P, d->align_corners, c.s);
+                                d->P, d->align_corners, inv_den, c.s);
         }
         if (d->C != 1)
             rc = render_fwd_c(c.w.S, c.w.ld_s, P.nbox, P.rec + (L.REC - 1), P.rec + (L.REC - 2), L.ld_rec, x, recon, st->train ? c.w.aux : nullptr,
-                              c.w.bce_partial, d->B, L.HW, d->C, d->I, d->P, d->align_corners, c.s);
+                              c.w.bce_partial, d->B, L.HW, d->C, d->I, d->P, d->align_corners, inv_den, c.s);
         else if (rc == SPAIR_ERR_UNSUPPORTED)
             rc = render_fwd(c.w.S, c.w.ld_s, P.nbox, P.rec + (L.REC - 1), P.rec + (L.REC - 2), L.ld_rec, x, recon, st->train ? c.w.aux : nullptr,
-                            c.w.bce_partial, d->B, L.HW, d->C, d->I, d->P, d->align_corners, d->dtype == SPAIR_BF16 && !d->obj_conv, c.s);
+                            c.w.bce_partial, d->B, L.HW, d->C, d->I, d->P, d->align_corners, d->dtype == SPAIR_BF16 && !d->obj_conv, inv_den, c.s);
         TRY(rc);
     }
     if (side && hipStreamWaitEvent(c.s, side->ev[1], 0) != hipSuccess) return SPAIR_ERR_LAUNCH;
@@ -1384,9 +1394,19 @@ extern "C" int spair_backward(const SpairDims* d, const SpairStep* st, const flo
 extern "C" int spair_backward_ev(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
                                  const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace,
                                  const float* grad_loss, float* grads, void* stream, void* ev_decoder, void* ev_cells, void* ev_backbone) {
+    return spair_backward_out(d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, grad_loss, grads, stream, ev_decoder, ev_cells,
+                              ev_backbone, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int spair_backward_out(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
+                                  const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace,
+                                  const float* grad_loss, float* grads, void* stream, void* ev_decoder, void* ev_cells, void* ev_backbone,
+                                  const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
+                                  float* aux_scratch) {
     Ctx c;
     TRY(make_ctx(c, d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, stream));
     if (!grad_loss || !grads) return SPAIR_ERR_SHAPE;
+    if (grad_recon && (!inv_den || !aux_scratch)) return SPAIR_ERR_SHAPE;
     const CellLayout& L = c.L;
     CellBufs& P = c.w.cb;
     const ParamLayout& PL = c.PL;
@@ -1395,18 +1415,30 @@ extern "C" int spair_backward_ev(const SpairDims* d, const SpairStep* st, const 
     const int per = d->P * d->P * (d->C + 1);
     // renderer -> d logits, d z_where, d z_pres, d z_depth
     const int b16 = d->dtype == SPAIR_BF16;
+    // an adjoint of the recon output: the renderer runs on a folded copy of aux with a loss gradient of 1 (outgrad.hip); the forward's aux
+    // and P.gloss (the KL terms' scale further down) stay as they are
+    const float* r_aux = c.w.aux;
+    const float* r_gloss = grad_loss;
+    if (grad_recon) {
+        const size_t n2 = (size_t)d->B * d->C * d->I * d->I * 2;
+        TRY(outgrad_recon_fold(c.w.aux, grad_loss, grad_recon, inv_den, aux_scratch, aux_scratch + n2, d->B, d->C, d->I, c.s));
+        r_aux = aux_scratch;
+        r_gloss = aux_scratch + n2;
+    }
     {
         ProfScope ps(PS_RENDER_BWD, c.s);
         if (d->C != 1)
-            TRY(render_bwd_c(c.w.S, c.w.ld_s, P.nbox, P.rec + (L.REC - 1), P.rec + (L.REC - 2), L.ld_rec, c.w.aux, grad_loss, c.w.dLog, P.g_nbox_r,
+            TRY(render_bwd_c(c.w.S, c.w.ld_s, P.nbox, P.rec + (L.REC - 1), P.rec + (L.REC - 2), L.ld_rec, r_aux, r_gloss, c.w.dLog, P.g_nbox_r,
                              P.g_pres_r, P.g_depth_r, c.w.ld_s, d->B, L.HW, d->C, d->I, d->P, d->align_corners, d->obj_logit_scale,
                              d->alpha_logit_scale, c.s));
         else
-        TRY(render_bwd(c.w.S, c.w.ld_s, P.nbox, P.rec + (L.REC - 1), P.rec + (L.REC - 2), L.ld_rec, c.w.aux, grad_loss, c.w.dLog, P.g_nbox_r,
+        TRY(render_bwd(c.w.S, c.w.ld_s, P.nbox, P.rec + (L.REC - 1), P.rec + (L.REC - 2), L.ld_rec, r_aux, r_gloss, c.w.dLog, P.g_nbox_r,
                        P.g_pres_r, P.g_depth_r, c.w.ld_s, d->B, L.HW, d->C, d->I, d->P, d->align_corners, d->obj_logit_scale,
                        d->alpha_logit_scale, b16 && !d->obj_conv, b16 && !d->obj_conv,
                        b16 && !d->obj_conv && d->C == 1 && render_prep_supported(L.HW, d->I, d->P, d->align_corners) ? c.w.rrec : nullptr, c.s));
     }
+    // adjoints of the z_where / z_pres outputs: added to the rows the renderer just wrote, before the per-cell backward reads them
+    TRY(outgrad_rows_fold(P.cell_h, P.cell_w, d->B, d->G, grad_z_where, grad_z_pres, P.g_nbox_r, P.g_pres_r, c.s));
     SideStream* side = nullptr;
     if (!(st->flags & 4)) TRY(side_stream(side));
     std::unique_lock<std::mutex> enq_lock;

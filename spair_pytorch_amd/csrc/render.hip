@@ -34,7 +34,8 @@ template <bool S16>
 __global__ __launch_bounds__(256) void k_render_fwd(const float* __restrict__ S, int ld_s, const float* __restrict__ nbox,
                                                     const float* __restrict__ pres, const float* __restrict__ depth, int ld_pd,
                                                     const float* __restrict__ x, float* __restrict__ recon, float2* __restrict__ aux,
-                                                    float* __restrict__ bce_partial, int B, int HW, int I, int P, int ac) {
+                                                    float* __restrict__ bce_partial, int B, int HW, int I, int P, int ac,
+                                                    float* __restrict__ inv_den) {
     __shared__ Cand cand[RCH];
     __shared__ unsigned short wlist[4][RCH];     // per wave (= a 16 x 4 pixel strip of the tile): the candidates that reach its rows
     __shared__ int wave_cnt[4][5];               // [culling wave][tile, strip 0..3]
@@ -165,6 +166,7 @@ __global__ __launch_bounds__(256) void k_render_fwd(const float* __restrict__ S,
             const float gr = (pre >= 0.f && pre <= 1.f) ? (r - xv) / fmaxf(r * (1.f - r), 1e-12f) : 0.f;
             aux[pi] = make_float2(gr * invD, pre);        // (dBCE/dpre / D, pre)
         }
+        if (inv_den) inv_den[pi] = invD;                  // differentiable recon output (outgrad.hip)
     }
     bce = block_reduce_sum_256(bce, red);
     if (threadIdx.x == 0) bce_partial[blockIdx.x] = bce;
@@ -432,29 +434,30 @@ int render_num_blocks(int B, int I) {
 }
 
 int render_fwd2(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* x,
-                float* recon, float* aux, float* bce_partial, int B, int HW, int I, int P, int ac, int s_bf16, hipStream_t s);
+                float* recon, float* aux, float* bce_partial, int B, int HW, int I, int P, int ac, int s_bf16, float* inv_den, hipStream_t s);
 int render_bwd2(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* aux,
                 const float* gloss, float* dlogits, float* dnbox, float* dpres, float* ddepth, int ld_g, int B, int HW, int I, int P,
                 int ac, float obj_scale, float alpha_scale, const void* rec, hipStream_t s);
 int render_prep(const float* nbox, const float* pres, const float* depth, int ld_pd, void* rec, int B, int HW, int I, int P, int ac,
                 hipStream_t s);
 int render_fwd_mma(const void* S16, int ld_s, const void* rec, const float* x, float* recon, float* aux, float* bce_partial, int B, int HW,
-                   int I, int P, int ac, hipStream_t s);
+                   int I, int P, int ac, float* inv_den, hipStream_t s);
 // s_bf16: sprites are bf16 (grey, alpha) pairs; ld_s stays in ELEMENTS of that type.  aux: B*I*I float2 (dBCE/dpre / D, pre).
+// inv_den (optional, B*I*I): 1/D per pixel, kept for the gradient of the recon output (outgrad.hip); every renderer forward writes it the same way.
 int render_fwd(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* x,
-               float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int ac, int s_bf16, hipStream_t s) {
+               float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int ac, int s_bf16, float* inv_den, hipStream_t s) {
     if (C != 1) return SPAIR_ERR_UNSUPPORTED;
     if (B <= 0 || HW <= 0 || I <= 0 || (ld_s & 1)) return SPAIR_ERR_SHAPE;
     {
-        const int rc = render_fwd2(S, ld_s, nbox, pres, depth, ld_pd, x, recon, aux, bce_partial, B, HW, I, P, ac, s_bf16, s);
+        const int rc = render_fwd2(S, ld_s, nbox, pres, depth, ld_pd, x, recon, aux, bce_partial, B, HW, I, P, ac, s_bf16, inv_den, s);
         if (rc != SPAIR_ERR_UNSUPPORTED) return rc;
     }
     if (s_bf16)
         hipLaunchKernelGGL(k_render_fwd<true>, dim3(render_num_blocks(B, I)), dim3(256), 0, s, S, ld_s, nbox, pres, depth, ld_pd, x, recon,
-                           reinterpret_cast<float2*>(aux), bce_partial, B, HW, I, P, ac);
+                           reinterpret_cast<float2*>(aux), bce_partial, B, HW, I, P, ac, inv_den);
     else
     hipLaunchKernelGGL(k_render_fwd<false>, dim3(render_num_blocks(B, I)), dim3(256), 0, s, S, ld_s, nbox, pres, depth, ld_pd, x, recon,
-                       reinterpret_cast<float2*>(aux), bce_partial, B, HW, I, P, ac);
+                       reinterpret_cast<float2*>(aux), bce_partial, B, HW, I, P, ac, inv_den);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
@@ -489,7 +492,7 @@ extern "C" int spair_render_fwd(const float* sprites, int ld_s, const float* nbo
                                 const float* x, float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P,
                                 int align_corners, void* stream) {
     return render_fwd(sprites, ld_s, nbox, pres, depth, 1, x, recon, aux, bce_partial, B, HW, C, I, P, align_corners, 0,
-                      (hipStream_t)stream);
+                      nullptr, (hipStream_t)stream);
 }
 extern "C" int spair_render_bwd(const float* sprites, int ld_s, const float* nbox, const float* pres, const float* depth,
                                 const float* aux, const float* grad_loss, float* dlogits, float* dnbox, float* dpres,
@@ -505,7 +508,7 @@ extern "C" int spair_render_fwd16(const void* sprites_f16, int ld_s, const float
                                   const float* x, float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P,
                                   int align_corners, void* stream) {
     return render_fwd(reinterpret_cast<const float*>(sprites_f16), ld_s, nbox, pres, depth, 1, x, recon, aux, bce_partial, B, HW, C, I, P,
-                      align_corners, 1, (hipStream_t)stream);
+                      align_corners, 1, nullptr, (hipStream_t)stream);
 }
 extern "C" int spair_render_bwd16(const void* sprites_f16, int ld_s, const float* nbox, const float* pres, const float* depth,
                                   const float* aux, const float* grad_loss, void* dlogits_bf16, float* dnbox, float* dpres,
@@ -527,7 +530,7 @@ extern "C" int spair_render_fwd16m(const void* sprites_f16, int ld_s, const void
                                    float* bce_partial, int B, int HW, int C, int I, int P, int align_corners, void* stream) {
     if (C != 1) return SPAIR_ERR_UNSUPPORTED;
     if (B <= 0 || HW <= 0 || I <= 0) return SPAIR_ERR_SHAPE;
-    return render_fwd_mma(sprites_f16, ld_s, records, x, recon, aux, bce_partial, B, HW, I, P, align_corners, (hipStream_t)stream);
+    return render_fwd_mma(sprites_f16, ld_s, records, x, recon, aux, bce_partial, B, HW, I, P, align_corners, nullptr, (hipStream_t)stream);
 }
 // spair_render_bwd16 reading the inverse-affine parameters and footprints from the records spair_render_prep wrote for the same nbox /
 // pres / depth (what the training step does); same outputs.

@@ -86,7 +86,7 @@ template <bool S16, int PT, int AC, int IP2>
 __global__ __launch_bounds__(256) void k_render_fwd3(const float* __restrict__ S, int ld_s, const float* __restrict__ nbox,
                                                      const float* __restrict__ pres, const float* __restrict__ depth, int ld_pd,
                                                      const float* __restrict__ x, float* __restrict__ recon, float2* __restrict__ aux,
-                                                     float* __restrict__ bce_partial, int B, int HW, int I, int Prt) {
+                                                     float* __restrict__ bce_partial, int B, int HW, int I, int Prt, float* __restrict__ inv_den) {
     extern __shared__ __attribute__((aligned(16))) char sm3[];
     constexpr int TEXB = S16 ? 4 : 8;                 // bytes per (grey, alpha) texel
     constexpr int ES = S16 ? 2 : 4;                   // bytes per sprite element
@@ -267,6 +267,7 @@ __global__ __launch_bounds__(256) void k_render_fwd3(const float* __restrict__ S
             const float gr = (pre >= 0.f && pre <= 1.f) ? (r - xv) / fmaxf(r * (1.f - r), 1e-12f) : 0.f;
             aux[pi] = make_float2(gr * invD, pre);
         }
+        if (inv_den) inv_den[pi] = invD;
     }
     bce = block_reduce_sum_256(bce, red);
     if (tid == 0) bce_partial[blockIdx.x] = bce;
@@ -274,7 +275,7 @@ __global__ __launch_bounds__(256) void k_render_fwd3(const float* __restrict__ S
 
 // SPAIR_ERR_UNSUPPORTED: the caller falls back to the first-generation kernel
 int render_fwd2(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* x,
-                float* recon, float* aux, float* bce_partial, int B, int HW, int I, int P, int ac, int s_bf16, hipStream_t s) {
+                float* recon, float* aux, float* bce_partial, int B, int HW, int I, int P, int ac, int s_bf16, float* inv_den, hipStream_t s) {
     const int texb = s_bf16 ? 4 : 8, es = s_bf16 ? 2 : 4;
     if ((P * texb) % 16 != 0 || ((size_t)ld_s * es) % 16 != 0 || P > RF3_ROWS || P < 2 || P > 255) return SPAIR_ERR_UNSUPPORTED;
     if ((unsigned long long)B * HW * ld_s * es >= (1ull << 32)) return SPAIR_ERR_UNSUPPORTED;
@@ -293,7 +294,7 @@ int render_fwd2(const float* S, int ld_s, const float* nbox, const float* pres, 
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3) != hipSuccess)                                   \
             return SPAIR_ERR_LAUNCH;                                                                                                    \
         hipLaunchKernelGGL((k_render_fwd3<S16_, PT_, AC_, IP2_>), grid, block, lds3, s, S, ld_s, nbox, pres, depth, ld_pd, x, recon,     \
-                           aux2, bce_partial, B, HW, I, P);                                                                             \
+                           aux2, bce_partial, B, HW, I, P, inv_den);                                                                    \
     } while (0)
         if (s_bf16) {
             if (P == 28 && !ac && ip2) RF3_LAUNCH(true, 28, 0, 1);

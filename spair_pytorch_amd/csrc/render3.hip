@@ -95,7 +95,7 @@ template <int IP2, int NT>
 __global__ __launch_bounds__(256) void k_render_fwd_mma(const void* __restrict__ S, unsigned s_bytes, const RenderObjRec* __restrict__ orec,
                                                         const RenderCullRec* __restrict__ crec, const float* __restrict__ x,
                                                         float* __restrict__ recon, float2* __restrict__ aux,
-                                                        float* __restrict__ bce_partial, int B, int HW, int I) {
+                                                        float* __restrict__ bce_partial, int B, int HW, int I, float* __restrict__ inv_den) {
     __shared__ unsigned list[4][R3_MAXHW / 4];
     __shared__ int cnt[4];
     __shared__ float red[4][NT][8][64];
@@ -285,6 +285,7 @@ __global__ __launch_bounds__(256) void k_render_fwd_mma(const void* __restrict__
                 const float gr = (pre >= 0.f && pre <= 1.f) ? (r - xv[t]) * r3_rcp(fmaxf(r * (1.f - r), 1e-12f)) : 0.f;
                 aux[pi[t]] = make_float2(gr * invD, pre);
             }
+            if (inv_den) inv_den[pi[t]] = invD;
         }
     }
     bce = block_reduce_sum_256(bce, red4);
@@ -319,7 +320,7 @@ int render_prep(const float* nbox, const float* pres, const float* depth, int ld
 #define R3_NT 4                     // 16-row tiles per workgroup region (one tile column, R3_NT tiles tall)
 #endif
 int render_fwd_mma(const void* S16, int ld_s, const void* rec, const float* x, float* recon, float* aux, float* bce_partial, int B, int HW,
-                   int I, int P, int ac, hipStream_t s) {
+                   int I, int P, int ac, float* inv_den, hipStream_t s) {
     if (ac || P != R3_P || ld_s != R3_P * R3_P * 2 || HW > R3_MAXHW || I >= (int)R3_EMPTY) return SPAIR_ERR_UNSUPPORTED;
     if ((unsigned long long)B * HW * R3_SPRB >= 0xfffffff0ull - 64) return SPAIR_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(S16) & 15) || (reinterpret_cast<uintptr_t>(rec) & 15)) return SPAIR_ERR_UNSUPPORTED;
@@ -334,7 +335,7 @@ int render_fwd_mma(const void* S16, int ld_s, const void* rec, const float* x, f
     const bool ip2 = (I & (I - 1)) == 0;
 #define R3_LAUNCH(IP2_, NT_)                                                                                                           \
     hipLaunchKernelGGL((k_render_fwd_mma<IP2_, NT_>), grid, block, 0, s, S16, s_bytes, orec, crec, x, recon, reinterpret_cast<float2*>(aux), \
-                       bce_partial, B, HW, I)
+                       bce_partial, B, HW, I, inv_den)
     if (nt == 1) { if (ip2) R3_LAUNCH(1, 1); else R3_LAUNCH(0, 1); }
     else { if (ip2) R3_LAUNCH(1, R3_NT); else R3_LAUNCH(0, R3_NT); }
 #undef R3_LAUNCH

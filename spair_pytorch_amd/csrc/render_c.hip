@@ -21,7 +21,8 @@ template <int C>
 __global__ __launch_bounds__(256) void k_render_fwd_c(const float* __restrict__ S, int ld_s, const float* __restrict__ nbox,
                                                       const float* __restrict__ pres, const float* __restrict__ depth, int ld_pd,
                                                       const float* __restrict__ x, float* __restrict__ recon, float2* __restrict__ aux,
-                                                      float* __restrict__ bce_partial, int B, int HW, int I, int P, int ac) {
+                                                      float* __restrict__ bce_partial, int B, int HW, int I, int P, int ac,
+                                                      float* __restrict__ inv_den) {
     constexpr int CH = C + 1;
     __shared__ Cand cand[RCH];
     __shared__ float red[4];
@@ -91,6 +92,7 @@ __global__ __launch_bounds__(256) void k_render_fwd_c(const float* __restrict__ 
     if (inside) {
         const float D = den + (float)HW * 1e-9f;          // every object adds 1e-9 (models.py:527)
         const float invD = 1.f / D;
+        if (inv_den) inv_den[((size_t)b * I + py) * I + px] = invD;      // one denominator per pixel, shared by the colour channels
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             const float pre = num[c] * invD;
@@ -233,15 +235,15 @@ __global__ __launch_bounds__(64) void k_render_bwd_c(const float* __restrict__ S
 
 int render_num_blocks(int B, int I);
 
-// sprites fp32 [N][ld_s] = [P*P][C+1]; x / recon [B][C][I][I]; aux: B*C*I*I float2 (dBCE/dpre / D, pre) or null
+// sprites fp32 [N][ld_s] = [P*P][C+1]; x / recon [B][C][I][I]; aux: B*C*I*I float2 (dBCE/dpre / D, pre) or null; inv_den: B*I*I 1/D or null
 int render_fwd_c(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* x, float* recon,
-                 float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int ac, hipStream_t s) {
+                 float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int ac, float* inv_den, hipStream_t s) {
     if (C < 2 || C > RC_MAXC) return SPAIR_ERR_UNSUPPORTED;
     if (B <= 0 || HW <= 0 || I <= 0 || P <= 0 || ld_s < P * P * (C + 1)) return SPAIR_ERR_SHAPE;
     const dim3 grid(render_num_blocks(B, I));
     float2* a2 = reinterpret_cast<float2*>(aux);
-    if (C == 2) hipLaunchKernelGGL(k_render_fwd_c<2>, grid, dim3(256), 0, s, S, ld_s, nbox, pres, depth, ld_pd, x, recon, a2, bce_partial, B, HW, I, P, ac);
-    else hipLaunchKernelGGL(k_render_fwd_c<3>, grid, dim3(256), 0, s, S, ld_s, nbox, pres, depth, ld_pd, x, recon, a2, bce_partial, B, HW, I, P, ac);
+    if (C == 2) hipLaunchKernelGGL(k_render_fwd_c<2>, grid, dim3(256), 0, s, S, ld_s, nbox, pres, depth, ld_pd, x, recon, a2, bce_partial, B, HW, I, P, ac, inv_den);
+    else hipLaunchKernelGGL(k_render_fwd_c<3>, grid, dim3(256), 0, s, S, ld_s, nbox, pres, depth, ld_pd, x, recon, a2, bce_partial, B, HW, I, P, ac, inv_den);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
@@ -265,7 +267,7 @@ int render_bwd_c(const float* S, int ld_s, const float* nbox, const float* pres,
 extern "C" int spair_render_fwd_rgb(const float* sprites, int ld_s, const float* nbox, const float* pres, const float* depth, const float* x,
                                     float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int align_corners,
                                     void* stream) {
-    return render_fwd_c(sprites, ld_s, nbox, pres, depth, 1, x, recon, aux, bce_partial, B, HW, C, I, P, align_corners, (hipStream_t)stream);
+    return render_fwd_c(sprites, ld_s, nbox, pres, depth, 1, x, recon, aux, bce_partial, B, HW, C, I, P, align_corners, nullptr, (hipStream_t)stream);
 }
 extern "C" int spair_render_bwd_rgb(const float* sprites, int ld_s, const float* nbox, const float* pres, const float* depth, const float* aux,
                                     const float* grad_loss, float* dlogits, float* dnbox, float* dpres, float* ddepth, int B, int HW, int C,

@@ -11,6 +11,9 @@ step, train.py:64-67) runs unchanged.  All arithmetic of the step is in libspair
 * ``forward`` enqueues ``spair_forward`` (backbone -> 3G-2 dependency wavefronts of the
   per-cell encoder -> decoder -> fused inverse-STN compositor -> KL/loss); ``loss.backward()``
   enqueues ``spair_backward`` (hand-written reverse pass) which accumulates into ``p.grad``;
+* with ``differentiable_outputs=True`` the recon / z_where / z_pres outputs are autograd tensors
+  too, as in the reference: adjoints that reach them are folded into that same reverse pass
+  (``spair_forward_out`` / ``spair_backward_out``);
 * there is no PyTorch/CPU fallback: without the HIP library or a GPU this module raises.
 """
 import ctypes
@@ -114,7 +117,9 @@ class _Engine(dict):
 class _StepFn(torch.autograd.Function):
     """Ties the hand-written backward into autograd.  ``anchor`` is a dummy differentiable leaf:
     the parameter gradients are accumulated straight into the flat gradient buffer (the views
-    behind every ``p.grad``) by ``spair_backward`` instead of being returned one tensor at a time."""
+    behind every ``p.grad``) by ``spair_backward`` instead of being returned one tensor at a time.
+    recon / z_where / z_pres are differentiable only with ``model.differentiable_outputs``; their
+    adjoints then enter the same reverse pass (``spair_backward_out``)."""
 
     @staticmethod
     def forward(ctx, anchor, model, x, step, noise):
@@ -125,8 +130,11 @@ class _StepFn(torch.autograd.Function):
         # A weak reference: the graph must not keep a multi-GB workspace alive after the cache evicted it.
         ctx.engine_ref = weakref.ref(model._last["engine"])
         ctx.generation = model._last["engine"]["generation"]
-        ctx.mark_non_differentiable(recon, z_where, z_pres)
-        ctx.set_materialize_grads(False)     # otherwise autograd zero-fills a gradient for each non-differentiable output (17 MB per step)
+        if not model.differentiable_outputs:
+            ctx.mark_non_differentiable(recon, z_where, z_pres)
+        # otherwise autograd zero-fills a gradient for each output nothing reached (17 MB per step): an absent adjoint stays None and
+        # launches nothing
+        ctx.set_materialize_grads(False)
         model._loss_terms = loss_terms
         # a view, not a copy: `loss_terms` is a fresh buffer of this forward (a device copy here is 6 us + a launch gap between the loss
         # kernel and the backward's first kernel).  Slot 9 is the kernel's SECOND copy of the total: an in-place op on the returned loss
@@ -135,7 +143,7 @@ class _StepFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, g_recon, g_zw, g_zp):
-        if g_loss is None:
+        if g_loss is None and g_recon is None and g_zw is None and g_zp is None:
             return None, None, None, None, None
         engine = ctx.engine_ref()
         if engine is None or engine["generation"] != ctx.generation:
@@ -143,17 +151,26 @@ class _StepFn(torch.autograd.Function):
                 "backward() of a SPAIR forward whose saved activations were overwritten by a later forward of the same batch size, or "
                 "whose workspace the engine cache has dropped (the engine keeps ONE set of activations per batch size and "
                 "`max_engines` batch sizes; call backward before the next forward of that size)")
-        ctx.model._run_backward(ctx.x, ctx.step, ctx.noise, g_loss.contiguous().float(), engine)
+        if g_loss is None:        # a backward through the outputs alone: the loss terms (KL scale included) get a zero adjoint
+            g_loss = torch.zeros((), device=ctx.x.device, dtype=torch.float32)
+        outs = [None if g is None else g.contiguous().float() for g in (g_recon, g_zw, g_zp)]
+        ctx.model._run_backward(ctx.x, ctx.step, ctx.noise, g_loss.contiguous().float(), engine, *outs)
         return None, None, None, None, None      # the parameter gradients went straight into the flat buffer
 
 
 class SPAIR(nn.Module):
-    def __init__(self, image_shape, writer=None, device=None, compute_dtype=None, object_encoder=None):
+    def __init__(self, image_shape, writer=None, device=None, compute_dtype=None, object_encoder=None, differentiable_outputs=False):
         """``object_encoder``: 'mlp' (the reference's live configuration, models.py:152,165) or 'conv' -- the convolutional encoder /
         decoder pair of ``cfg.CONV_OBJECT_ENCODER_TOPOLOGY`` (config.py:15-20) that models.py:606-665 sketches but cannot run
         (parity unpinned); default ``cfg.OBJECT_ENCODER``.  The conv pair runs on the per-wavefront launches in either compute dtype (its
-        own convolutions in fp32; the fused bf16 per-cell kernels are built for the MLP pair)."""
+        own convolutions in fp32; the fused bf16 per-cell kernels are built for the MLP pair).
+
+        ``differentiable_outputs``: with grad enabled, ``recon``, ``z_where`` and ``z_pres`` require grad as in the reference
+        (models.py:35-131) and a user term on them trains through the model (box supervision, a count loss, a masked recon loss).
+        Off by default: the outputs are then plain tensors (``.numpy()`` works on them directly) and the step is unchanged.  On, it
+        costs one [B,I,I] store in the renderer forward, plus two elementwise kernels in a backward that receives such an adjoint."""
         super().__init__()
+        self.differentiable_outputs = bool(differentiable_outputs)
         self.object_encoder_kind = (object_encoder or cfg.OBJECT_ENCODER).lower()
         if self.object_encoder_kind not in ('mlp', 'conv'):
             raise ValueError("object_encoder must be 'mlp' or 'conv'")
@@ -361,10 +378,21 @@ class SPAIR(nn.Module):
                      workspace=ws,                                                   # zero-initialised ONCE per engine
                      noise=dict(eps_box=torch.empty(batch, 4, G, G, device=dev), eps_attr=torch.empty(batch, A, G, G, device=dev),
                                 eps_depth=torch.empty(batch, 1, G, G, device=dev), u_pres=torch.empty(batch, 1, G, G, device=dev)))
+            if self.differentiable_outputs:
+                self._outgrad_buffers(e)
         else:
             self._engines.pop(batch)
         self._engines[batch] = e         # most recently used last
         return e
+
+    def _outgrad_buffers(self, e):
+        """The differentiable outputs' two buffers of engine ``e`` (allocated on first use): the renderer's 1/D per pixel, kept by the
+        forward, and the backward's folded copy of the renderer's per-pixel adjoints (+ one float for its unit loss gradient)."""
+        if e.get("inv_den") is None:
+            d = e['dims']
+            e["inv_den"] = torch.empty(d.B, d.I, d.I, device=self.device, dtype=torch.float32)
+            e["aux_scratch"] = torch.empty(2 * d.B * d.C * d.I * d.I + 1, device=self.device, dtype=torch.float32)
+        return e["inv_den"], e["aux_scratch"]
 
     def _draw_noise(self, e):
         """The 7 per-cell draws (models.py:333-336,84,95,402-403) as whole maps, one launch; the seed
@@ -389,21 +417,25 @@ class SPAIR(nn.Module):
         st.status_host = ctypes.cast(self._status_host, ctypes.c_void_p).value
         e["generation"] += 1              # whatever this workspace held for an earlier forward is gone now
         self._last = dict(engine=e, st=st)
-        L.check(L.lib().spair_forward(ctypes.byref(d), ctypes.byref(st), L.ptr(self._flat), L.ptr(x), L.ptr(noise['eps_box']),
-                                      L.ptr(noise['eps_attr']), L.ptr(noise['eps_depth']), L.ptr(noise['u_pres']),
-                                      L.ptr(e['workspace']), L.ptr(loss_terms), L.ptr(recon), L.ptr(z_where), L.ptr(z_pres),
-                                      L.stream()), "spair_forward")
+        inv_den = self._outgrad_buffers(e)[0] if train and self.differentiable_outputs else None
+        L.check(L.lib().spair_forward_out(ctypes.byref(d), ctypes.byref(st), L.ptr(self._flat), L.ptr(x), L.ptr(noise['eps_box']),
+                                          L.ptr(noise['eps_attr']), L.ptr(noise['eps_depth']), L.ptr(noise['u_pres']),
+                                          L.ptr(e['workspace']), L.ptr(loss_terms), L.ptr(recon), L.ptr(z_where), L.ptr(z_pres),
+                                          L.stream(), L.ptr(inv_den)), "spair_forward")
         return loss_terms, recon, z_where, z_pres
 
-    def _run_backward(self, x, step, noise, g_loss, e=None):
+    def _run_backward(self, x, step, noise, g_loss, e=None, g_recon=None, g_z_where=None, g_z_pres=None):
+        """``g_recon`` / ``g_z_where`` / ``g_z_pres``: contiguous fp32 adjoints of the forward's outputs, or None (nothing launched for them)."""
         e = e if e is not None else self._engine(x.shape[0])
         st = step_scalars(step, x.shape[0], self.world_size, True)
         self._bind_grads()
         gb = self._grad_buckets
         ev = gb.handles() if gb is not None else [ctypes.c_void_p(0)] * 3
-        L.check(L.lib().spair_backward_ev(ctypes.byref(e['dims']), ctypes.byref(st), L.ptr(self._flat), L.ptr(x), L.ptr(noise['eps_box']),
-                                          L.ptr(noise['eps_attr']), L.ptr(noise['eps_depth']), L.ptr(noise['u_pres']),
-                                          L.ptr(e['workspace']), L.ptr(g_loss), L.ptr(self._flat_grad), L.stream(), ev[0], ev[1], ev[2]),
+        L.check(L.lib().spair_backward_out(ctypes.byref(e['dims']), ctypes.byref(st), L.ptr(self._flat), L.ptr(x), L.ptr(noise['eps_box']),
+                                           L.ptr(noise['eps_attr']), L.ptr(noise['eps_depth']), L.ptr(noise['u_pres']),
+                                           L.ptr(e['workspace']), L.ptr(g_loss), L.ptr(self._flat_grad), L.stream(), ev[0], ev[1], ev[2],
+                                           L.ptr(e.get('inv_den')), L.ptr(g_recon), L.ptr(g_z_where), L.ptr(g_z_pres),
+                                           L.ptr(e.get('aux_scratch'))),
                 "spair_backward")
         if gb is not None:
             gb.pending = True             # ddp.allreduce_gradients(model) consumes the three events
