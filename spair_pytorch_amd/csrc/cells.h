@@ -1,5 +1,5 @@
 // Buffers and hyper-parameters shared by the per-cell kernels (cells.hip, stn.hip, render.hip,
-// loss.hip) and the host orchestration (engine.hip).
+// loss.hip, outgrad.hip) and the host orchestration (engine.hip), and the launchers engine.hip calls in them.
 #pragma once
 #include "layout.h"
 
@@ -64,3 +64,15 @@ int cells_bwd_depth(const CellLayout& L, const CellBufs& P, const CellHyper& H, 
 int cells_bwd_attr(const CellLayout& L, const CellBufs& P, const CellHyper& H, int r0, int R, hipStream_t s);
 int cells_bwd_box(const CellLayout& L, const CellBufs& P, const CellHyper& H, int r0, int R, hipStream_t s);
 int cells_dfeat_edge(const CellLayout& L, const CellBufs& P, float* gedge, hipStream_t s);
+
+// stn.hip (rows r0 .. r0+R-1, row r reads image r % B), outgrad.hip, loss.hip
+int stn_glimpse_fwd(const float* x, const float* nbox, int B, float* out, int ld, int r0, int R, int C, int I, int P, int ac, int px16, hipStream_t s);
+int stn_glimpse_bwd(const float* x, const float* nbox, int B, const float* dgl, int ld, float* dnbox, int r0, int R, int C, int I, int P, int ac, int px16, hipStream_t s);
+int outgrad_recon_fold(const float* aux, const float* gloss, const float* grad_recon, const float* inv_den, float* aux_ext, float* one, int B,
+                       int C, int I, hipStream_t s);
+int outgrad_rows_fold(const int* cell_h, const int* cell_w, int B, int G, const float* g_z_where, const float* g_z_pres, float* g_nbox_r,
+                      float* g_pres_r, hipStream_t s);
+int loss_count_kl(const CellLayout& L, const CellBufs& P, float prior_prob, float* klp, hipStream_t s);
+int loss_gauss_kl_blocks(const CellLayout& L);
+int loss_gauss_kl(const CellLayout& L, const CellBufs& P, const CellHyper& H, float* partial, hipStream_t s);
+int loss_finalize(const float* bce_partial, int n_bce, const float* kl_partial, int n_kl, const float* klp, int B, float kl_scale, float beta, float* loss_out, const int* failed, int* status, int* status_host, hipStream_t s);

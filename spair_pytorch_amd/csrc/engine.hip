@@ -16,30 +16,7 @@
 #include "chain.h"
 #include "dec_fused.h"
 #include "objconv.h"
-
-// kernels in other translation units
-int stn_glimpse_fwd(const float* x, const float* nbox, int B, float* out, int ld, int r0, int R, int C, int I, int P, int ac, int px16, hipStream_t s);
-int stn_glimpse_bwd(const float* x, const float* nbox, int B, const float* dgl, int ld, float* dnbox, int r0, int R, int C, int I, int P, int ac, int px16, hipStream_t s);
-int render_sprite_act(float* S, int ld, int N, int per, int CH, float obj_scale, float alpha_scale, float alpha_bias, hipStream_t s);
-int render_num_blocks(int B, int I);
-int render_fwd(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* x, float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int ac, int s_bf16, float* inv_den, hipStream_t s);
-int render_prep(const float* nbox, const float* pres, const float* depth, int ld_pd, void* rec, int B, int HW, int I, int P, int ac, hipStream_t s);
-int render_fwd_mma(const void* S16, int ld_s, const void* rec, const float* x, float* recon, float* aux, float* bce_partial, int B, int HW, int I, int P, int ac, float* inv_den, hipStream_t s);
-int render_bwd(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* aux, const float* gloss, float* dlogits, float* dnbox, float* dpres, float* ddepth, int ld_g, int B, int HW, int C, int I, int P, int ac, float obj_scale, float alpha_scale, int g_bf16, int s_bf16, const void* rec, hipStream_t s);
-int render_prep_supported(int HW, int I, int P, int ac);
-int render_fwd_c(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* x, float* recon,
-                 float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int ac, float* inv_den, hipStream_t s);
-int render_bwd_c(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* aux,
-                 const float* gloss, float* dlogits, float* dnbox, float* dpres, float* ddepth, int ld_g, int B, int HW, int C, int I, int P,
-                 int ac, float obj_scale, float alpha_scale, hipStream_t s);
-int outgrad_recon_fold(const float* aux, const float* gloss, const float* grad_recon, const float* inv_den, float* aux_ext, float* one, int B,
-                       int C, int I, hipStream_t s);
-int outgrad_rows_fold(const int* cell_h, const int* cell_w, int B, int G, const float* g_z_where, const float* g_z_pres, float* g_nbox_r,
-                      float* g_pres_r, hipStream_t s);
-int loss_count_kl(const CellLayout& L, const CellBufs& P, float prior_prob, float* klp, hipStream_t s);
-int loss_gauss_kl_blocks(const CellLayout& L);
-int loss_gauss_kl(const CellLayout& L, const CellBufs& P, const CellHyper& H, float* partial, hipStream_t s);
-int loss_finalize(const float* bce_partial, int n_bce, const float* kl_partial, int n_kl, const float* klp, int B, float kl_scale, float beta, float* loss_out, const int* failed, int* status, int* status_host, hipStream_t s);
+#include "render.h"
 
 #define TRY(expr)                      \
     do {                               \
@@ -289,9 +266,8 @@ static Ws carve(const SpairDims& d, void* base) {
     b.mbits = chain_fwd_supported(d) ? c.take<unsigned long long>((size_t)d.B * nbands * (3 * d.G - 2) * 66 * 4) : nullptr;
     w.Hd1 = reinterpret_cast<float*>(c.take_bytes(N * SP_DEC_H1 * es)); w.Hd2 = reinterpret_cast<float*>(c.take_bytes(N * SP_DEC_H2 * es));
     w.S = c.take<float>(N * w.ld_s);
-    // (the conv decoder takes fp32 sprite gradients in both modes; the generic-channel renderer of colour images writes fp32 ones, which the
-    //  bf16 step's decoder backward reads through a bf16 copy)
-    w.dLog = reinterpret_cast<float*>(c.take_bytes(N * w.ld_s * ((d.obj_conv || d.C != 1) ? 4 : es)));
+    // (fp32 outside render_16bit; the bf16 step's decoder backward reads the colour renderer's through the bf16 copy dLog16)
+    w.dLog = reinterpret_cast<float*>(c.take_bytes(N * w.ld_s * (render_16bit(d) ? 2 : 4)));
     w.dLog16 = (d.dtype == SPAIR_BF16 && d.C != 1) ? c.take_bytes(N * w.ld_s * 2) : nullptr;
     w.dHd2 = reinterpret_cast<float*>(c.take_bytes(N * SP_DEC_H2 * es)); w.dHd1 = reinterpret_cast<float*>(c.take_bytes(N * SP_DEC_H1 * es));
     w.Za16 = c.take_bytes(N * L.ld_rec * 2); w.dfeat16 = c.take_bytes(N * w.ld_feat * 2);
@@ -300,7 +276,7 @@ static Ws carve(const SpairDims& d, void* base) {
     w.tn_part2 = reinterpret_cast<float*>(c.take_bytes((size_t)SPAIR_TN_PART_FLOATS * 4));
     w.aux = c.take<float>((size_t)d.B * d.C * d.I * d.I * 2);     // float2 per pixel and colour channel: (dBCE/dpre / D, pre)
     w.bce_partial = c.take<float>(render_num_blocks(d.B, d.I));
-    w.rrec = c.take_bytes((size_t)N * 64);                  // the renderer's per-object records (render3.hip)
+    w.rrec = c.take_bytes(render_prep_bytes(d.B, L.HW));      // the renderer's per-object records (render3.hip)
     for (int i = 0; i < PL.oc_n; ++i) {
         const ConvSpec& e = PL.oc_enc[i];
         const size_t n = N * e.hout * e.hout * e.cout;
@@ -421,6 +397,8 @@ struct Ctx {
     int T;                 // number of wavefront diagonals
     int use_chain;         // fused persistent per-cell kernels (bf16, reference network sizes)
     int use_dec_fused;     // the decoder forward as one activation-stationary kernel (bf16; SpairStep.flags bit 4 turns it off)
+    RenderGeom rg;         // the renderer's objects: the rows' nbox, presence and depth
+    RenderPlan rp;         // the renderer's kernels and sprite / d-logit formats (render.h)
     float* tn_scratch = nullptr;   // split-K scratch override while work is being issued on the helper stream
     std::vector<int> dstart;
 };
@@ -512,8 +490,10 @@ static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const float
     c.w.cb.eps_box = eps_box; c.w.cb.eps_attr = eps_attr; c.w.cb.eps_depth = eps_depth; c.w.cb.u_pres = u_pres;
     fill_diag(c);
     c.use_chain = chain_fwd_supported(*d) && !(st->flags & 1) && !d->obj_conv;
-    c.use_dec_fused = !d->obj_conv && d->dtype == SPAIR_BF16 && !(st->flags & 16) && c.PL.lin[LIN_DEC0].out == SP_DEC_H1 && c.PL.lin[LIN_DEC1].out == SP_DEC_H2 &&
-                      dec_fused_supported(d->A, d->P * d->P * (d->C + 1), c.L.ld_rec, c.L.N, c.w.ld_s) && d->C == 1;
+    c.rg = {c.w.cb.nbox, c.w.cb.rec + (c.L.REC - 1), c.w.cb.rec + (c.L.REC - 2), c.L.ld_rec, d->B, c.L.HW, d->I, d->P, d->align_corners};
+    c.rp = render_plan(*d, c.rg, c.w.ld_s, c.w.S, c.w.rrec, c.w.dLog);
+    c.use_dec_fused = c.rp.s16 /* it writes fp16 sprites */ && !(st->flags & 16) && c.PL.lin[LIN_DEC0].out == SP_DEC_H1 && c.PL.lin[LIN_DEC1].out == SP_DEC_H2 &&
+                      dec_fused_supported(d->A, d->P * d->P * (d->C + 1), c.L.ld_rec, c.L.N, c.w.ld_s);
     return SPAIR_OK;
 }
 
@@ -1181,7 +1161,6 @@ extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const 
     // the KL terms only need the cell chain's outputs: they run on the helper stream beside the decoder and the renderer.  (The count-prior
     // KL is one dependent chain per sample, ~0.17 ms beside the decoder at configs[1] and as long as decoder + renderer together: nothing
     // may sit in front of it on the helper stream -- the renderer's record kernel, 6 us, runs on the caller's stream instead.)
-    int rc_prep = SPAIR_ERR_UNSUPPORTED;
     {
         hipStream_t ks = side ? side->s : c.s;
         if (side) TRY(stream_link(c.s, ks, side->ev[0]));
@@ -1193,10 +1172,7 @@ extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const 
         if (side && hipEventRecord(side->ev[1], ks) != hipSuccess) return SPAIR_ERR_LAUNCH;
         if (gauss_on_main) TRY(loss_gauss_kl(L, P, c.H, c.w.kl_partial, c.s));
     }
-    if (d->dtype == SPAIR_BF16 && d->C == 1 && !d->obj_conv) {      // (the conv decoder's sprites are fp32: tap renderer)
-        rc_prep = render_prep(P.nbox, P.rec + (L.REC - 1), P.rec + (L.REC - 2), L.ld_rec, c.w.rrec, d->B, L.HW, d->I, d->P, d->align_corners, c.s);
-        if (rc_prep != SPAIR_OK && rc_prep != SPAIR_ERR_UNSUPPORTED) return rc_prep;
-    }
+    if (c.rp.rec) TRY(render_prep(c.rg, c.w.rrec, c.s));
     // decoder (models.py:474-492)
     const ParamLayout& PL = c.PL;
     const int N = L.N;
@@ -1228,8 +1204,8 @@ extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const 
             memset(&g, 0, sizeof(g));
             g.A = c.w.Hd2; g.lda = SP_DEC_H2; g.B = c.w.lin_wf[LIN_DEC2]; g.ldb = K2; g.C = c.w.S; g.ldc = c.w.ld_s; g.M = N; g.N = per; g.K = K2;
             g.bias = params + PL.lin[LIN_DEC2].b; g.sprite_ch = d->C + 1;
-            g.c_bf16 = b16 && d->C == 1;      // bf16 step: the sprites leave as 16-bit (grey, alpha) pairs -- half the bytes for the renderer, both
-                                              // ways (colour images: fp32 sprites for the generic-channel renderer)
+            g.c_bf16 = c.rp.s16;      // bf16 step: the sprites leave as 16-bit (grey, alpha) pairs -- half the bytes for the renderer, both
+                                      // ways (colour images: fp32 sprites for the generic-channel renderer)
             g.obj_scale = d->obj_logit_scale; g.alpha_scale = d->alpha_logit_scale; g.alpha_bias = d->alpha_logit_bias;
             if (b16) TRY(spair_gemm_nt16_impl(g, false, c.s));
             else TRY(spair_gemm_nt_impl(g, false, d->dtype, c.s));
@@ -1239,19 +1215,11 @@ extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const 
     // KL + render + loss
     {
         ProfScope ps(PS_RENDER_FWD, c.s);
-        // bf16 step: the sampling on the matrix cores from per-object records (render3.hip); every other case on the tap kernels
-        int rc = SPAIR_ERR_UNSUPPORTED;
-        if (rc_prep == SPAIR_OK) {
-            rc = render_fwd_mma(c.w.S, c.w.ld_s, c.w.rrec, x, recon, st->train ? c.w.aux : nullptr, c.w.bce_partial, d->B, L.HW, d->I,
-                                d->P, d->align_corners, inv_den, c.s);
-        }
-        if (d->C != 1)
-            rc = render_fwd_c(c.w.S, c.w.ld_s, P.nbox, P.rec + (L.REC - 1), P.rec + (L.REC - 2), L.ld_rec, x, recon, st->train ? c.w.aux : nullptr,
-                              c.w.bce_partial, d->B, L.HW, d->C, d->I, d->P, d->align_corners, inv_den, c.s);
-        else if (rc == SPAIR_ERR_UNSUPPORTED)
-            rc = render_fwd(c.w.S, c.w.ld_s, P.nbox, P.rec + (L.REC - 1), P.rec + (L.REC - 2), L.ld_rec, x, recon, st->train ? c.w.aux : nullptr,
-                            c.w.bce_partial, d->B, L.HW, d->C, d->I, d->P, d->align_corners, d->dtype == SPAIR_BF16 && !d->obj_conv, inv_den, c.s);
-        TRY(rc);
+        float* const aux = st->train ? c.w.aux : nullptr;
+        if (c.rp.fwd == RENDER_MMA) TRY(render_fwd_mma(c.rg, c.w.S, c.w.ld_s, c.w.rrec, x, recon, aux, c.w.bce_partial, inv_den, c.s));
+        else if (c.rp.fwd == RENDER_GEN2) TRY(render_fwd2(c.rg, c.w.S, c.w.ld_s, c.rp.s16, x, recon, aux, c.w.bce_partial, inv_den, c.s));
+        else if (c.rp.fwd == RENDER_GEN1) TRY(render_fwd1(c.rg, c.w.S, c.w.ld_s, c.rp.s16, x, recon, aux, c.w.bce_partial, inv_den, c.s));
+        else TRY(render_fwd_c(c.rg, c.w.S, c.w.ld_s, d->C, x, recon, aux, c.w.bce_partial, inv_den, c.s));
     }
     if (side && hipStreamWaitEvent(c.s, side->ev[1], 0) != hipSuccess) return SPAIR_ERR_LAUNCH;
     ProfScope psl(PS_LOSS, c.s);
@@ -1427,15 +1395,14 @@ extern "C" int spair_backward_out(const SpairDims* d, const SpairStep* st, const
     }
     {
         ProfScope ps(PS_RENDER_BWD, c.s);
-        if (d->C != 1)
-            TRY(render_bwd_c(c.w.S, c.w.ld_s, P.nbox, P.rec + (L.REC - 1), P.rec + (L.REC - 2), L.ld_rec, r_aux, r_gloss, c.w.dLog, P.g_nbox_r,
-                             P.g_pres_r, P.g_depth_r, c.w.ld_s, d->B, L.HW, d->C, d->I, d->P, d->align_corners, d->obj_logit_scale,
-                             d->alpha_logit_scale, c.s));
-        else
-        TRY(render_bwd(c.w.S, c.w.ld_s, P.nbox, P.rec + (L.REC - 1), P.rec + (L.REC - 2), L.ld_rec, r_aux, r_gloss, c.w.dLog, P.g_nbox_r,
-                       P.g_pres_r, P.g_depth_r, c.w.ld_s, d->B, L.HW, d->C, d->I, d->P, d->align_corners, d->obj_logit_scale,
-                       d->alpha_logit_scale, b16 && !d->obj_conv, b16 && !d->obj_conv,
-                       b16 && !d->obj_conv && d->C == 1 && render_prep_supported(L.HW, d->I, d->P, d->align_corners) ? c.w.rrec : nullptr, c.s));
+        const float so = d->obj_logit_scale, sa = d->alpha_logit_scale;
+        if (c.rp.bwd == RENDER_GEN2)
+            TRY(render_bwd2(c.rg, c.w.S, c.w.ld_s, c.rp.rec ? c.w.rrec : nullptr, r_aux, r_gloss, c.w.dLog, P.g_nbox_r, P.g_pres_r, P.g_depth_r,
+                            c.w.ld_s, so, sa, c.s));
+        else if (c.rp.bwd == RENDER_GEN1)
+            TRY(render_bwd1(c.rg, c.w.S, c.w.ld_s, c.rp.s16, r_aux, r_gloss, c.w.dLog, P.g_nbox_r, P.g_pres_r, P.g_depth_r, c.w.ld_s, so, sa,
+                            c.rp.g16, c.s));
+        else TRY(render_bwd_c(c.rg, c.w.S, c.w.ld_s, d->C, r_aux, r_gloss, c.w.dLog, P.g_nbox_r, P.g_pres_r, P.g_depth_r, c.w.ld_s, so, sa, c.s));
     }
     // adjoints of the z_where / z_pres outputs: added to the rows the renderer just wrote, before the per-cell backward reads them
     TRY(outgrad_rows_fold(P.cell_h, P.cell_w, d->B, d->G, grad_z_where, grad_z_pres, P.g_nbox_r, P.g_pres_r, c.s));
@@ -1453,7 +1420,7 @@ extern "C" int spair_backward_out(const SpairDims* d, const SpairStep* st, const
                  // weight gradients go to the helper stream and overlap with the (latency-bound) per-cell backward chain
         const LinSpec &l2 = PL.lin[LIN_DEC2], &l1 = PL.lin[LIN_DEC1], &l0 = PL.lin[LIN_DEC0];
         float* const dlog_f32 = c.w.dLog;
-        if (d->C != 1) {      // the generic-channel renderer left fp32 sprite gradients
+        if (!c.rp.g16) {      // the generic-channel renderer left fp32 sprite gradients
             TRY(spair_to_bf16(c.w.dLog, c.w.ld_s, c.w.dLog16, c.w.ld_s, N, c.w.ld_s, c.s));
             c.w.dLog = reinterpret_cast<float*>(c.w.dLog16);
         }

@@ -11,7 +11,7 @@
 //    (cell position cp = r / B, sample b = r % B) and cp -> (h, w) through the workspace's cell tables -- the mapping the forward's
 //    z_where / z_pres export uses on both the per-wavefront launches and the fused chain, for every N_LOOKBACK.
 // Plain elementwise kernels: one element (or row) per thread, no atomics, so the step stays bit-for-bit repeatable.
-#include "common.h"
+#include "cells.h"
 
 __global__ __launch_bounds__(256) void k_recon_fold(const float2* __restrict__ aux, const float* __restrict__ gloss,
                                                     const float* __restrict__ grad_recon, const float* __restrict__ inv_den,

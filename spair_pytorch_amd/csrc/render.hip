@@ -433,73 +433,69 @@ int render_num_blocks(int B, int I) {
     return B * t * t;
 }
 
-int render_fwd2(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* x,
-                float* recon, float* aux, float* bce_partial, int B, int HW, int I, int P, int ac, int s_bf16, float* inv_den, hipStream_t s);
-int render_bwd2(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* aux,
-                const float* gloss, float* dlogits, float* dnbox, float* dpres, float* ddepth, int ld_g, int B, int HW, int I, int P,
-                int ac, float obj_scale, float alpha_scale, const void* rec, hipStream_t s);
-int render_prep(const float* nbox, const float* pres, const float* depth, int ld_pd, void* rec, int B, int HW, int I, int P, int ac,
-                hipStream_t s);
-int render_fwd_mma(const void* S16, int ld_s, const void* rec, const float* x, float* recon, float* aux, float* bce_partial, int B, int HW,
-                   int I, int P, int ac, float* inv_den, hipStream_t s);
-// s_bf16: sprites are bf16 (grey, alpha) pairs; ld_s stays in ELEMENTS of that type.  aux: B*I*I float2 (dBCE/dpre / D, pre).
-// inv_den (optional, B*I*I): 1/D per pixel, kept for the gradient of the recon output (outgrad.hip); every renderer forward writes it the same way.
-int render_fwd(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* x,
-               float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int ac, int s_bf16, float* inv_den, hipStream_t s) {
-    if (C != 1) return SPAIR_ERR_UNSUPPORTED;
-    if (B <= 0 || HW <= 0 || I <= 0 || (ld_s & 1)) return SPAIR_ERR_SHAPE;
-    {
-        const int rc = render_fwd2(S, ld_s, nbox, pres, depth, ld_pd, x, recon, aux, bce_partial, B, HW, I, P, ac, s_bf16, inv_den, s);
-        if (rc != SPAIR_ERR_UNSUPPORTED) return rc;
-    }
-    if (s_bf16)
-        hipLaunchKernelGGL(k_render_fwd<true>, dim3(render_num_blocks(B, I)), dim3(256), 0, s, S, ld_s, nbox, pres, depth, ld_pd, x, recon,
-                           reinterpret_cast<float2*>(aux), bce_partial, B, HW, I, P, ac, inv_den);
-    else
-    hipLaunchKernelGGL(k_render_fwd<false>, dim3(render_num_blocks(B, I)), dim3(256), 0, s, S, ld_s, nbox, pres, depth, ld_pd, x, recon,
-                       reinterpret_cast<float2*>(aux), bce_partial, B, HW, I, P, ac, inv_den);
+int render_fwd1(const RenderGeom& g, const float* S, int ld_s, int s16, const float* x, float* recon, float* aux, float* bce_partial,
+                float* inv_den, hipStream_t s) {
+    hipLaunchKernelGGL(s16 ? k_render_fwd<true> : k_render_fwd<false>, dim3(render_num_blocks(g.B, g.I)), dim3(256), 0, s, S, ld_s, g.nbox,
+                       g.pres, g.depth, g.ld_pd, x, recon, reinterpret_cast<float2*>(aux), bce_partial, g.B, g.HW, g.I, g.P, g.ac, inv_den);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
 
-int render_bwd(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* aux,
-               const float* gloss, float* dlogits, float* dnbox, float* dpres, float* ddepth, int ld_g, int B, int HW, int C, int I,
-               int P, int ac, float obj_scale, float alpha_scale, int g_bf16, int s_bf16, const void* rec, hipStream_t s) {
-    if (C != 1) return SPAIR_ERR_UNSUPPORTED;
+int render_bwd1(const RenderGeom& g, const float* S, int ld_s, int s16, const float* aux, const float* gloss, float* dlogits, float* dnbox,
+                float* dpres, float* ddepth, int ld_g, float obj_scale, float alpha_scale, int g16, hipStream_t s) {
     if ((ld_s & 1) || (ld_g & 1)) return SPAIR_ERR_ALIGN;
-    if (g_bf16 && s_bf16) {   // the bf16 step: one wave per object, sampling on VALU, its transpose on the matrix cores
-        // rec (optional): the per-object records the forward's k_render_prep left in the workspace
-        const int rc = render_bwd2(S, ld_s, nbox, pres, depth, ld_pd, aux, gloss, dlogits, dnbox, dpres, ddepth, ld_g, B, HW, I, P, ac,
-                                   obj_scale, alpha_scale, rec, s);
-        if (rc != SPAIR_ERR_UNSUPPORTED) return rc;
-    }
-    if (I > RB_CAP || (long long)I * I > 0x7fffffffLL / 4 || HW > 65535) return SPAIR_ERR_UNSUPPORTED;
-    const size_t lds = ((size_t)(P + 2) * (P + 2) * 4 + 3 * RB_CAP + I) * sizeof(float);
+    if (g.I > RB_CAP || (long long)g.I * g.I > 0x7fffffffLL / 4 || g.HW > 65535) return SPAIR_ERR_UNSUPPORTED;
+    const size_t lds = ((size_t)(g.P + 2) * (g.P + 2) * 4 + 3 * RB_CAP + g.I) * sizeof(float);
     if (lds > 65536) return SPAIR_ERR_UNSUPPORTED;
-    if (s_bf16)
-        hipLaunchKernelGGL(k_render_bwd<true>, dim3(B, HW), dim3(RB_T), lds, s, S, ld_s, nbox, pres, depth, ld_pd,
-                           reinterpret_cast<const float2*>(aux), gloss, dlogits, dnbox, dpres, ddepth, ld_g, B, HW, I, P, ac, obj_scale,
-                           alpha_scale, g_bf16);
-    else
-    hipLaunchKernelGGL(k_render_bwd<false>, dim3(B, HW), dim3(RB_T), lds, s, S, ld_s, nbox, pres, depth, ld_pd,
-                       reinterpret_cast<const float2*>(aux), gloss, dlogits, dnbox, dpres, ddepth, ld_g, B, HW, I, P, ac, obj_scale,
-                       alpha_scale, g_bf16);
+    hipLaunchKernelGGL(s16 ? k_render_bwd<true> : k_render_bwd<false>, dim3(g.B, g.HW), dim3(RB_T), lds, s, S, ld_s, g.nbox, g.pres, g.depth,
+                       g.ld_pd, reinterpret_cast<const float2*>(aux), gloss, dlogits, dnbox, dpres, ddepth, ld_g, g.B, g.HW, g.I, g.P, g.ac,
+                       obj_scale, alpha_scale, g16);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
+}
+
+// The training step's renderer: in each direction the first family whose predicate accepts.  The workspace's
+// buffers share its base's alignment, so when the records are not written for an unaligned base, k_render_bwd2 refuses the sprites too.
+RenderPlan render_plan(const SpairDims& d, const RenderGeom& g, int ld_s, const float* S, const void* rec, const float* dlogits) {
+    RenderPlan p;
+    p.s16 = p.g16 = render_16bit(d);
+    p.rec = p.s16 && render_prep_supported(g) && !(reinterpret_cast<uintptr_t>(rec) & 15);
+    p.fwd = d.C != 1 ? RENDER_COLOUR
+          : p.rec && render_fwd_mma_supported(g, S, ld_s, rec) ? RENDER_MMA
+          : render_fwd2_supported(g, S, ld_s, p.s16) ? RENDER_GEN2 : RENDER_GEN1;
+    p.bwd = d.C != 1 ? RENDER_COLOUR : p.s16 && render_bwd2_supported(g, S, ld_s, dlogits, ld_s) ? RENDER_GEN2 : RENDER_GEN1;
+    return p;
+}
+
+// unit-level C ABI (tests): the grey entry points try k_render_fwd3 / k_render_bwd2 first and fall back to the first generation.  b16: fp16
+// sprites in, bf16 d-logits out; rec: records for k_render_bwd2 or null.
+static int render_fwd_grey(const RenderGeom& g, const float* S, int ld_s, int s16, int C, const float* x, float* recon, float* aux,
+                           float* bce_partial, hipStream_t s) {
+    if (C != 1) return SPAIR_ERR_UNSUPPORTED;
+    if (g.B <= 0 || g.HW <= 0 || g.I <= 0 || (ld_s & 1)) return SPAIR_ERR_SHAPE;
+    if (render_fwd2_supported(g, S, ld_s, s16)) return render_fwd2(g, S, ld_s, s16, x, recon, aux, bce_partial, nullptr, s);
+    return render_fwd1(g, S, ld_s, s16, x, recon, aux, bce_partial, nullptr, s);
+}
+static int render_bwd_grey(const RenderGeom& g, const float* S, int ld_s, int b16, const void* rec, int C, const float* aux, const float* gloss,
+                           float* dlogits, float* dnbox, float* dpres, float* ddepth, float obj_scale, float alpha_scale, hipStream_t s) {
+    if (C != 1) return SPAIR_ERR_UNSUPPORTED;
+    if (b16 && render_bwd2_supported(g, S, ld_s, dlogits, ld_s))
+        return render_bwd2(g, S, ld_s, rec, aux, gloss, dlogits, dnbox, dpres, ddepth, ld_s, obj_scale, alpha_scale, s);
+    return render_bwd1(g, S, ld_s, b16, aux, gloss, dlogits, dnbox, dpres, ddepth, ld_s, obj_scale, alpha_scale, b16, s);
 }
 
 extern "C" int spair_render_fwd(const float* sprites, int ld_s, const float* nbox, const float* pres, const float* depth,
                                 const float* x, float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P,
                                 int align_corners, void* stream) {
-    return render_fwd(sprites, ld_s, nbox, pres, depth, 1, x, recon, aux, bce_partial, B, HW, C, I, P, align_corners, 0,
-                      nullptr, (hipStream_t)stream);
+    return render_fwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners}, sprites, ld_s, 0, C, x, recon, aux, bce_partial,
+                           (hipStream_t)stream);
 }
 extern "C" int spair_render_bwd(const float* sprites, int ld_s, const float* nbox, const float* pres, const float* depth,
                                 const float* aux, const float* grad_loss, float* dlogits, float* dnbox, float* dpres,
                                 float* ddepth, int B, int HW, int C, int I, int P, int align_corners, float obj_scale,
                                 float alpha_scale, void* stream) {
-    return render_bwd(sprites, ld_s, nbox, pres, depth, 1, aux, grad_loss, dlogits, dnbox, dpres, ddepth, ld_s, B, HW, C, I, P,
-                      align_corners, obj_scale, alpha_scale, 0, 0, nullptr, (hipStream_t)stream);
+    return render_bwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners}, sprites, ld_s, 0, nullptr, C, aux, grad_loss, dlogits, dnbox,
+                           dpres, ddepth, obj_scale, alpha_scale, (hipStream_t)stream);
 }
 
 // 16-bit sprite variants (what the bf16 training step runs): sprites are fp16 (grey, alpha) pairs [N][ld_s] (ld_s in elements), the
@@ -507,16 +503,16 @@ extern "C" int spair_render_bwd(const float* sprites, int ld_s, const float* nbo
 extern "C" int spair_render_fwd16(const void* sprites_f16, int ld_s, const float* nbox, const float* pres, const float* depth,
                                   const float* x, float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P,
                                   int align_corners, void* stream) {
-    return render_fwd(reinterpret_cast<const float*>(sprites_f16), ld_s, nbox, pres, depth, 1, x, recon, aux, bce_partial, B, HW, C, I, P,
-                      align_corners, 1, nullptr, (hipStream_t)stream);
+    return render_fwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners}, reinterpret_cast<const float*>(sprites_f16), ld_s, 1, C, x,
+                           recon, aux, bce_partial, (hipStream_t)stream);
 }
 extern "C" int spair_render_bwd16(const void* sprites_f16, int ld_s, const float* nbox, const float* pres, const float* depth,
                                   const float* aux, const float* grad_loss, void* dlogits_bf16, float* dnbox, float* dpres,
                                   float* ddepth, int B, int HW, int C, int I, int P, int align_corners, float obj_scale,
                                   float alpha_scale, void* stream) {
-    return render_bwd(reinterpret_cast<const float*>(sprites_f16), ld_s, nbox, pres, depth, 1, aux, grad_loss,
-                      reinterpret_cast<float*>(dlogits_bf16), dnbox, dpres, ddepth, ld_s, B, HW, C, I, P, align_corners, obj_scale,
-                      alpha_scale, 1, 1, nullptr, (hipStream_t)stream);
+    return render_bwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners}, reinterpret_cast<const float*>(sprites_f16), ld_s, 1, nullptr,
+                           C, aux, grad_loss, reinterpret_cast<float*>(dlogits_bf16), dnbox, dpres, ddepth, obj_scale, alpha_scale,
+                           (hipStream_t)stream);
 }
 // The matrix-core forward renderer of the bf16 step (render3.hip): spair_render_prep writes the per-object records (32 bytes each,
 // B * HW of them, caller-owned), spair_render_fwd16m composites from them.  SPAIR_ERR_UNSUPPORTED (P != 28, align_corners, HW > 1024):
@@ -524,21 +520,22 @@ extern "C" int spair_render_bwd16(const void* sprites_f16, int ld_s, const float
 extern "C" int spair_render_prep(const float* nbox, const float* pres, const float* depth, void* records, int B, int HW, int I, int P,
                                  int align_corners, void* stream) {
     if (B <= 0 || HW <= 0 || I <= 0) return SPAIR_ERR_SHAPE;
-    return render_prep(nbox, pres, depth, 1, records, B, HW, I, P, align_corners, (hipStream_t)stream);
+    return render_prep({nbox, pres, depth, 1, B, HW, I, P, align_corners}, records, (hipStream_t)stream);
 }
 extern "C" int spair_render_fwd16m(const void* sprites_f16, int ld_s, const void* records, const float* x, float* recon, float* aux,
                                    float* bce_partial, int B, int HW, int C, int I, int P, int align_corners, void* stream) {
     if (C != 1) return SPAIR_ERR_UNSUPPORTED;
     if (B <= 0 || HW <= 0 || I <= 0) return SPAIR_ERR_SHAPE;
-    return render_fwd_mma(sprites_f16, ld_s, records, x, recon, aux, bce_partial, B, HW, I, P, align_corners, nullptr, (hipStream_t)stream);
+    return render_fwd_mma({nullptr, nullptr, nullptr, 1, B, HW, I, P, align_corners}, sprites_f16, ld_s, records, x, recon, aux, bce_partial,
+                          nullptr, (hipStream_t)stream);
 }
-// spair_render_bwd16 reading the inverse-affine parameters and footprints from the records spair_render_prep wrote for the same nbox /
+// spair_render_bwd16 reading the inverse-affine parameters and pixel footprints from the records spair_render_prep wrote for the same nbox /
 // pres / depth (what the training step does); same outputs.
 extern "C" int spair_render_bwd16r(const void* sprites_f16, int ld_s, const float* nbox, const float* pres, const float* depth,
                                    const void* records, const float* aux, const float* grad_loss, void* dlogits_bf16, float* dnbox,
                                    float* dpres, float* ddepth, int B, int HW, int C, int I, int P, int align_corners, float obj_scale,
                                    float alpha_scale, void* stream) {
-    return render_bwd(reinterpret_cast<const float*>(sprites_f16), ld_s, nbox, pres, depth, 1, aux, grad_loss,
-                      reinterpret_cast<float*>(dlogits_bf16), dnbox, dpres, ddepth, ld_s, B, HW, C, I, P, align_corners, obj_scale,
-                      alpha_scale, 1, 1, records, (hipStream_t)stream);
+    return render_bwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners}, reinterpret_cast<const float*>(sprites_f16), ld_s, 1, records,
+                           C, aux, grad_loss, reinterpret_cast<float*>(dlogits_bf16), dnbox, dpres, ddepth, obj_scale, alpha_scale,
+                           (hipStream_t)stream);
 }

@@ -19,10 +19,6 @@
 #include <stdlib.h>
 #include "render_common.h"
 
-int render_prep_supported(int HW, int I, int P, int ac);                        // render3.hip
-const void* render_rec_cull(const void* rec, int B, int HW);
-const void* render_rec_bwd(const void* rec, int B, int HW);
-
 #define RF_TC 32          // objects per tile pass (<= 64: the per-strip cull is one ballot)
 
 struct RfCand {
@@ -273,42 +269,30 @@ __global__ __launch_bounds__(256) void k_render_fwd3(const float* __restrict__ S
     if (tid == 0) bce_partial[blockIdx.x] = bce;
 }
 
-// SPAIR_ERR_UNSUPPORTED: the caller falls back to the first-generation kernel
-int render_fwd2(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* x,
-                float* recon, float* aux, float* bce_partial, int B, int HW, int I, int P, int ac, int s_bf16, float* inv_den, hipStream_t s) {
-    const int texb = s_bf16 ? 4 : 8, es = s_bf16 ? 2 : 4;
-    if ((P * texb) % 16 != 0 || ((size_t)ld_s * es) % 16 != 0 || P > RF3_ROWS || P < 2 || P > 255) return SPAIR_ERR_UNSUPPORTED;
-    if ((unsigned long long)B * HW * ld_s * es >= (1ull << 32)) return SPAIR_ERR_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(S) & 15) != 0) return SPAIR_ERR_UNSUPPORTED;
+bool render_fwd2_supported(const RenderGeom& g, const float* S, int ld_s, int s16) {
+    const int P = g.P, texb = s16 ? 4 : 8, es = s16 ? 2 : 4;
+    if ((P * texb) % 16 != 0 || ((size_t)ld_s * es) % 16 != 0 || P > RF3_ROWS || P < 2 || P > 255) return false;
+    if ((unsigned long long)g.B * g.HW * ld_s * es >= (1ull << 32)) return false;
+    if ((reinterpret_cast<uintptr_t>(S) & 15) != 0) return false;
+    return (size_t)rf3_shared_bytes() + 4 * (size_t)rf3_wave_bytes(P, texb) <= 160 * 1024;
+}
+int render_fwd2(const RenderGeom& g, const float* S, int ld_s, int s16, const float* x, float* recon, float* aux, float* bce_partial,
+                float* inv_den, hipStream_t s) {
+    if (!render_fwd2_supported(g, S, ld_s, s16)) return SPAIR_ERR_UNSUPPORTED;
+    const int B = g.B, I = g.I, P = g.P, ac = g.ac;
     const int t = (I + RT - 1) / RT;
     const dim3 grid(B * t * t), block(256);
-    float2* aux2 = reinterpret_cast<float2*>(aux);
-    {
-        const size_t lds3 = (size_t)rf3_shared_bytes() + 4 * (size_t)rf3_wave_bytes(P, texb);
-        if (lds3 > 160 * 1024) return SPAIR_ERR_UNSUPPORTED;
-        const bool ip2 = (I & (I - 1)) == 0;
-#define RF3_LAUNCH(S16_, PT_, AC_, IP2_)                                                                                                \
-    do {                                                                                                                                \
-        if (lds3 > 64 * 1024 &&                                                                                                         \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_render_fwd3<S16_, PT_, AC_, IP2_>),                                    \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3) != hipSuccess)                                   \
-            return SPAIR_ERR_LAUNCH;                                                                                                    \
-        hipLaunchKernelGGL((k_render_fwd3<S16_, PT_, AC_, IP2_>), grid, block, lds3, s, S, ld_s, nbox, pres, depth, ld_pd, x, recon,     \
-                           aux2, bce_partial, B, HW, I, P, inv_den);                                                                    \
-    } while (0)
-        if (s_bf16) {
-            if (P == 28 && !ac && ip2) RF3_LAUNCH(true, 28, 0, 1);
-            else if (ac) RF3_LAUNCH(true, 0, 1, 0);
-            else RF3_LAUNCH(true, 0, 0, 0);
-        } else {
-            if (P == 28 && !ac && ip2) RF3_LAUNCH(false, 28, 0, 1);
-            else if (ac) RF3_LAUNCH(false, 0, 1, 0);
-            else RF3_LAUNCH(false, 0, 0, 0);
-        }
-#undef RF3_LAUNCH
-        SPAIR_CHECK_LAUNCH();
-        return SPAIR_OK;
-    }
+    const size_t lds3 = (size_t)rf3_shared_bytes() + 4 * (size_t)rf3_wave_bytes(P, s16 ? 4 : 8);
+    const bool pt28 = P == 28 && !ac && (I & (I - 1)) == 0;
+    auto* k = s16 ? (pt28 ? k_render_fwd3<true, 28, 0, 1> : ac ? k_render_fwd3<true, 0, 1, 0> : k_render_fwd3<true, 0, 0, 0>)
+                  : (pt28 ? k_render_fwd3<false, 28, 0, 1> : ac ? k_render_fwd3<false, 0, 1, 0> : k_render_fwd3<false, 0, 0, 0>);
+    if (lds3 > 64 * 1024 &&
+        hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3) != hipSuccess)
+        return SPAIR_ERR_LAUNCH;
+    hipLaunchKernelGGL(k, grid, block, lds3, s, S, ld_s, g.nbox, g.pres, g.depth, g.ld_pd, x, recon, reinterpret_cast<float2*>(aux), bce_partial,
+                       B, g.HW, I, P, inv_den);
+    SPAIR_CHECK_LAUNCH();
+    return SPAIR_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -620,27 +604,26 @@ __global__ __launch_bounds__(64, RB2_WAVES_PER_SIMD) void k_render_bwd2(const fl
     }
 }
 
-// bf16 sprites in, bf16 d-logits out.  SPAIR_ERR_UNSUPPORTED: the caller falls back to the first-generation kernel.
-int render_bwd2(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* aux,
-                const float* gloss, float* dlogits, float* dnbox, float* dpres, float* ddepth, int ld_g, int B, int HW, int I, int P,
-                int ac, float obj_scale, float alpha_scale, const void* rec, hipStream_t s) {
-    if ((P & 3) || P > 32 || P < 4 || (ld_s & 7) || (ld_g & 7) || HW > 65535) return SPAIR_ERR_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(S) & 15) || (reinterpret_cast<uintptr_t>(dlogits) & 15)) return SPAIR_ERR_UNSUPPORTED;
+bool render_bwd2_supported(const RenderGeom& g, const float* S, int ld_s, const float* dlogits, int ld_g) {
+    const int P = g.P;
+    if ((P & 3) || P > 32 || P < 4 || (ld_s & 7) || (ld_g & 7) || g.HW > 65535) return false;
+    if ((reinterpret_cast<uintptr_t>(S) & 15) || (reinterpret_cast<uintptr_t>(dlogits) & 15)) return false;
+    return (size_t)rb2_lds_bytes(P) <= 64 * 1024 && (size_t)P * P * 4 <= RB2_ADJ_BYTES;
+}
+// rec (optional): the per-object records k_render_prep wrote for the same objects
+int render_bwd2(const RenderGeom& g, const float* S, int ld_s, const void* rec, const float* aux, const float* gloss, float* dlogits, float* dnbox,
+                float* dpres, float* ddepth, int ld_g, float obj_scale, float alpha_scale, hipStream_t s) {
+    if (!render_bwd2_supported(g, S, ld_s, dlogits, ld_g)) return SPAIR_ERR_UNSUPPORTED;
+    const int B = g.B, HW = g.HW, I = g.I, P = g.P, ac = g.ac;
     const size_t lds = (size_t)rb2_lds_bytes(P);
-    if (lds > 64 * 1024 || (size_t)P * P * 4 > RB2_ADJ_BYTES) return SPAIR_ERR_UNSUPPORTED;
     const dim3 grid(B, HW), block(64);
-    const bool use_rec = rec && render_prep_supported(HW, I, P, ac);
+    const bool use_rec = rec && render_prep_supported(g);
     const uint4* crec = use_rec ? reinterpret_cast<const uint4*>(render_rec_cull(rec, B, HW)) : nullptr;
     const float4* brec = use_rec ? reinterpret_cast<const float4*>(render_rec_bwd(rec, B, HW)) : nullptr;
-#define RB2_LAUNCH(PT_, AC_, IP2_, REC_)                                                                                                  \
-    hipLaunchKernelGGL((k_render_bwd2<PT_, AC_, IP2_, REC_>), grid, block, lds, s, S, ld_s, nbox, pres, depth, ld_pd,                      \
-                       reinterpret_cast<const float2*>(aux), gloss, reinterpret_cast<__bf16*>(dlogits), dnbox, dpres, ddepth, ld_g, B, HW, I, \
-                       P, obj_scale, alpha_scale, crec, brec)
-    const bool ip2 = (I & (I - 1)) == 0;
-    if (P == 28 && !ac && ip2) { if (use_rec) RB2_LAUNCH(28, 0, 1, true); else RB2_LAUNCH(28, 0, 1, false); }
-    else if (ac) RB2_LAUNCH(0, 1, 0, false);
-    else { if (use_rec) RB2_LAUNCH(0, 0, 0, true); else RB2_LAUNCH(0, 0, 0, false); }
-#undef RB2_LAUNCH
+    auto* k = P == 28 && !ac && (I & (I - 1)) == 0 ? (use_rec ? k_render_bwd2<28, 0, 1, true> : k_render_bwd2<28, 0, 1, false>)
+              : ac ? k_render_bwd2<0, 1, 0, false> : use_rec ? k_render_bwd2<0, 0, 0, true> : k_render_bwd2<0, 0, 0, false>;
+    hipLaunchKernelGGL(k, grid, block, lds, s, S, ld_s, g.nbox, g.pres, g.depth, g.ld_pd, reinterpret_cast<const float2*>(aux), gloss,
+                       reinterpret_cast<__bf16*>(dlogits), dnbox, dpres, ddepth, ld_g, B, HW, I, P, obj_scale, alpha_scale, crec, brec);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }

@@ -104,8 +104,3 @@ __device__ __forceinline__ float r3_rcp(float d) {
     const float r = __builtin_amdgcn_rcpf(d);
     return fmaf(fmaf(-d, r, 1.f), r, r);
 }
-
-// host side (render3.hip)
-int render_prep_supported(int HW, int I, int P, int ac);
-const void* render_rec_cull(const void* rec, int B, int HW);
-const void* render_rec_bwd(const void* rec, int B, int HW);

@@ -298,20 +298,17 @@ const void* render_rec_cull(const void* rec, int B, int HW) { return reinterpret
 const void* render_rec_bwd(const void* rec, int B, int HW) {
     return reinterpret_cast<const RenderCullRec*>(render_rec_cull(rec, B, HW)) + (size_t)B * HW;
 }
-int render_prep_supported(int HW, int I, int P, int ac) { return !ac && P == R3_P && HW <= R3_MAXHW && I < (int)R3_EMPTY; }
+bool render_prep_supported(const RenderGeom& g) { return !g.ac && g.P == R3_P && g.HW <= R3_MAXHW && g.I < (int)R3_EMPTY; }
 
-// SPAIR_ERR_UNSUPPORTED: the caller keeps k_render_fwd3 (which needs no records)
-int render_prep(const float* nbox, const float* pres, const float* depth, int ld_pd, void* rec, int B, int HW, int I, int P, int ac,
-                hipStream_t s) {
-    if (!render_prep_supported(HW, I, P, ac) || (reinterpret_cast<uintptr_t>(rec) & 15)) return SPAIR_ERR_UNSUPPORTED;
+int render_prep(const RenderGeom& g, void* rec, hipStream_t s) {
+    if (!render_prep_supported(g) || (reinterpret_cast<uintptr_t>(rec) & 15)) return SPAIR_ERR_UNSUPPORTED;
+    const int B = g.B, HW = g.HW;
     const dim3 grid((B * HW + 255) / 256), block(256);
     RenderObjRec* orec = reinterpret_cast<RenderObjRec*>(rec);
     RenderCullRec* crec = reinterpret_cast<RenderCullRec*>(orec + (size_t)B * HW);
     RenderBwdRec* brec = reinterpret_cast<RenderBwdRec*>(crec + (size_t)B * HW);
-    if ((I & (I - 1)) == 0)
-        hipLaunchKernelGGL((k_render_prep<0, 1>), grid, block, 0, s, nbox, pres, depth, ld_pd, orec, crec, brec, B, HW, I, P);
-    else
-        hipLaunchKernelGGL((k_render_prep<0, 0>), grid, block, 0, s, nbox, pres, depth, ld_pd, orec, crec, brec, B, HW, I, P);
+    auto* k = (g.I & (g.I - 1)) == 0 ? k_render_prep<0, 1> : k_render_prep<0, 0>;
+    hipLaunchKernelGGL(k, grid, block, 0, s, g.nbox, g.pres, g.depth, g.ld_pd, orec, crec, brec, B, HW, g.I, g.P);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
@@ -319,26 +316,27 @@ int render_prep(const float* nbox, const float* pres, const float* depth, int ld
 #ifndef R3_NT
 #define R3_NT 4                     // 16-row tiles per workgroup region (one tile column, R3_NT tiles tall)
 #endif
-int render_fwd_mma(const void* S16, int ld_s, const void* rec, const float* x, float* recon, float* aux, float* bce_partial, int B, int HW,
-                   int I, int P, int ac, float* inv_den, hipStream_t s) {
-    if (ac || P != R3_P || ld_s != R3_P * R3_P * 2 || HW > R3_MAXHW || I >= (int)R3_EMPTY) return SPAIR_ERR_UNSUPPORTED;
-    if ((unsigned long long)B * HW * R3_SPRB >= 0xfffffff0ull - 64) return SPAIR_ERR_UNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(S16) & 15) || (reinterpret_cast<uintptr_t>(rec) & 15)) return SPAIR_ERR_UNSUPPORTED;
+bool render_fwd_mma_supported(const RenderGeom& g, const void* S16, int ld_s, const void* rec) {
+    if (g.ac || g.P != R3_P || ld_s != R3_P * R3_P * 2 || g.HW > R3_MAXHW || g.I >= (int)R3_EMPTY) return false;
+    if ((unsigned long long)g.B * g.HW * R3_SPRB >= 0xfffffff0ull - 64) return false;
+    if ((reinterpret_cast<uintptr_t>(S16) & 15) || (reinterpret_cast<uintptr_t>(rec) & 15)) return false;
+    const int t = (g.I + RT - 1) / RT, nx = (g.B & 7) == 0 ? 8 : 1, nt = (t % R3_NT) == 0 ? R3_NT : 1;     // the launcher's grid
+    return t * (t / nt) <= 65535 && g.B / nx <= 65535;
+}
+int render_fwd_mma(const RenderGeom& g, const void* S16, int ld_s, const void* rec, const float* x, float* recon, float* aux, float* bce_partial,
+                   float* inv_den, hipStream_t s) {
+    if (!render_fwd_mma_supported(g, S16, ld_s, rec)) return SPAIR_ERR_UNSUPPORTED;
+    const int B = g.B, HW = g.HW, I = g.I;
     const int t = (I + RT - 1) / RT, nx = (B & 7) == 0 ? 8 : 1;
     // regions of R3_NT tiles when they tile the image's tile rows exactly (the bce_partial slots are the tiles'), single tiles otherwise
     const int nt = (t % R3_NT) == 0 ? R3_NT : 1;
-    if (t * (t / nt) > 65535 || B / nx > 65535) return SPAIR_ERR_UNSUPPORTED;
     const dim3 grid(nx, t * (t / nt), B / nx), block(256);
     const unsigned s_bytes = (unsigned)((size_t)B * HW * R3_SPRB);
     const RenderObjRec* orec = reinterpret_cast<const RenderObjRec*>(rec);
     const RenderCullRec* crec = reinterpret_cast<const RenderCullRec*>(orec + (size_t)B * HW);
     const bool ip2 = (I & (I - 1)) == 0;
-#define R3_LAUNCH(IP2_, NT_)                                                                                                           \
-    hipLaunchKernelGGL((k_render_fwd_mma<IP2_, NT_>), grid, block, 0, s, S16, s_bytes, orec, crec, x, recon, reinterpret_cast<float2*>(aux), \
-                       bce_partial, B, HW, I, inv_den)
-    if (nt == 1) { if (ip2) R3_LAUNCH(1, 1); else R3_LAUNCH(0, 1); }
-    else { if (ip2) R3_LAUNCH(1, R3_NT); else R3_LAUNCH(0, R3_NT); }
-#undef R3_LAUNCH
+    auto* k = nt == 1 ? (ip2 ? k_render_fwd_mma<1, 1> : k_render_fwd_mma<0, 1>) : (ip2 ? k_render_fwd_mma<1, R3_NT> : k_render_fwd_mma<0, R3_NT>);
+    hipLaunchKernelGGL(k, grid, block, 0, s, S16, s_bytes, orec, crec, x, recon, reinterpret_cast<float2*>(aux), bce_partial, B, HW, I, inv_den);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }

@@ -233,32 +233,27 @@ __global__ __launch_bounds__(64) void k_render_bwd_c(const float* __restrict__ S
 
 }  // namespace
 
-int render_num_blocks(int B, int I);
-
 // sprites fp32 [N][ld_s] = [P*P][C+1]; x / recon [B][C][I][I]; aux: B*C*I*I float2 (dBCE/dpre / D, pre) or null; inv_den: B*I*I 1/D or null
-int render_fwd_c(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* x, float* recon,
-                 float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int ac, float* inv_den, hipStream_t s) {
+int render_fwd_c(const RenderGeom& g, const float* S, int ld_s, int C, const float* x, float* recon, float* aux, float* bce_partial,
+                 float* inv_den, hipStream_t s) {
     if (C < 2 || C > RC_MAXC) return SPAIR_ERR_UNSUPPORTED;
-    if (B <= 0 || HW <= 0 || I <= 0 || P <= 0 || ld_s < P * P * (C + 1)) return SPAIR_ERR_SHAPE;
-    const dim3 grid(render_num_blocks(B, I));
-    float2* a2 = reinterpret_cast<float2*>(aux);
-    if (C == 2) hipLaunchKernelGGL(k_render_fwd_c<2>, grid, dim3(256), 0, s, S, ld_s, nbox, pres, depth, ld_pd, x, recon, a2, bce_partial, B, HW, I, P, ac, inv_den);
-    else hipLaunchKernelGGL(k_render_fwd_c<3>, grid, dim3(256), 0, s, S, ld_s, nbox, pres, depth, ld_pd, x, recon, a2, bce_partial, B, HW, I, P, ac, inv_den);
+    if (g.B <= 0 || g.HW <= 0 || g.I <= 0 || g.P <= 0 || ld_s < g.P * g.P * (C + 1)) return SPAIR_ERR_SHAPE;
+    hipLaunchKernelGGL(C == 2 ? k_render_fwd_c<2> : k_render_fwd_c<3>, dim3(render_num_blocks(g.B, g.I)), dim3(256), 0, s, S, ld_s, g.nbox,
+                       g.pres, g.depth, g.ld_pd, x, recon, reinterpret_cast<float2*>(aux), bce_partial, g.B, g.HW, g.I, g.P, g.ac, inv_den);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
 
 // dlogits fp32 [N][ld_g] = [P*P][C+1]; dnbox [N][4]; dpres / ddepth [N]
-int render_bwd_c(const float* S, int ld_s, const float* nbox, const float* pres, const float* depth, int ld_pd, const float* aux,
-                 const float* gloss, float* dlogits, float* dnbox, float* dpres, float* ddepth, int ld_g, int B, int HW, int C, int I, int P,
-                 int ac, float obj_scale, float alpha_scale, hipStream_t s) {
+int render_bwd_c(const RenderGeom& g, const float* S, int ld_s, int C, const float* aux, const float* gloss, float* dlogits, float* dnbox,
+                 float* dpres, float* ddepth, int ld_g, float obj_scale, float alpha_scale, hipStream_t s) {
+    const int B = g.B, HW = g.HW, I = g.I, P = g.P;
     if (C < 2 || C > RC_MAXC) return SPAIR_ERR_UNSUPPORTED;
     if (B <= 0 || HW <= 0 || HW > 65535 || I <= 0 || P <= 0 || ld_s < P * P * (C + 1) || ld_g < P * P * (C + 1)) return SPAIR_ERR_SHAPE;
     const size_t lds = (size_t)P * P * (C + 2) * sizeof(float);
     if (lds > 64 * 1024) return SPAIR_ERR_UNSUPPORTED;
-    const float2* a2 = reinterpret_cast<const float2*>(aux);
-    if (C == 2) hipLaunchKernelGGL(k_render_bwd_c<2>, dim3(B, HW), dim3(64), lds, s, S, ld_s, nbox, pres, depth, ld_pd, a2, gloss, dlogits, dnbox, dpres, ddepth, ld_g, B, HW, I, P, ac, obj_scale, alpha_scale);
-    else hipLaunchKernelGGL(k_render_bwd_c<3>, dim3(B, HW), dim3(64), lds, s, S, ld_s, nbox, pres, depth, ld_pd, a2, gloss, dlogits, dnbox, dpres, ddepth, ld_g, B, HW, I, P, ac, obj_scale, alpha_scale);
+    hipLaunchKernelGGL(C == 2 ? k_render_bwd_c<2> : k_render_bwd_c<3>, dim3(B, HW), dim3(64), lds, s, S, ld_s, g.nbox, g.pres, g.depth, g.ld_pd,
+                       reinterpret_cast<const float2*>(aux), gloss, dlogits, dnbox, dpres, ddepth, ld_g, B, HW, I, P, g.ac, obj_scale, alpha_scale);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
@@ -267,11 +262,11 @@ int render_bwd_c(const float* S, int ld_s, const float* nbox, const float* pres,
 extern "C" int spair_render_fwd_rgb(const float* sprites, int ld_s, const float* nbox, const float* pres, const float* depth, const float* x,
                                     float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int align_corners,
                                     void* stream) {
-    return render_fwd_c(sprites, ld_s, nbox, pres, depth, 1, x, recon, aux, bce_partial, B, HW, C, I, P, align_corners, nullptr, (hipStream_t)stream);
+    return render_fwd_c({nbox, pres, depth, 1, B, HW, I, P, align_corners}, sprites, ld_s, C, x, recon, aux, bce_partial, nullptr, (hipStream_t)stream);
 }
 extern "C" int spair_render_bwd_rgb(const float* sprites, int ld_s, const float* nbox, const float* pres, const float* depth, const float* aux,
                                     const float* grad_loss, float* dlogits, float* dnbox, float* dpres, float* ddepth, int B, int HW, int C,
                                     int I, int P, int align_corners, float obj_scale, float alpha_scale, void* stream) {
-    return render_bwd_c(sprites, ld_s, nbox, pres, depth, 1, aux, grad_loss, dlogits, dnbox, dpres, ddepth, ld_s, B, HW, C, I, P, align_corners,
+    return render_bwd_c({nbox, pres, depth, 1, B, HW, I, P, align_corners}, sprites, ld_s, C, aux, grad_loss, dlogits, dnbox, dpres, ddepth, ld_s,
                         obj_scale, alpha_scale, (hipStream_t)stream);
 }

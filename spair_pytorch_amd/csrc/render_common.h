@@ -3,6 +3,7 @@
 #pragma once
 #include "cells.h"
 #include "stn_math.h"
+#include "render.h"
 
 #define RT 16            // output tile side
 #define RCH 256          // objects culled per pass (= threads per block)

@@ -270,7 +270,7 @@ __global__ __launch_bounds__(64, 2) void k_render_bwd_mma(const void* __restrict
 int render_bwd_mma(const void* S16, int ld_s, const void* rec, const float* aux, const float* gloss, void* dlogits16, float* dnbox,
                    float* dpres, float* ddepth, int ld_g, int B, int HW, int I, int P, int ac, float obj_scale, float alpha_scale,
                    hipStream_t s) {
-    if (!rec || !render_prep_supported(HW, I, P, ac) || ld_s != R3_P * R3_P * 2 || (ld_g & 7) || HW > 65535) return SPAIR_ERR_UNSUPPORTED;
+    if (!rec || !render_prep_supported({nullptr, nullptr, nullptr, 0, B, HW, I, P, ac}) || ld_s != R3_P * R3_P * 2 || (ld_g & 7) || HW > 65535) return SPAIR_ERR_UNSUPPORTED;
     if ((unsigned long long)B * HW * R3_SPRB >= 0xfffffff0ull - 64) return SPAIR_ERR_UNSUPPORTED;
     if ((reinterpret_cast<uintptr_t>(S16) & 15) || (reinterpret_cast<uintptr_t>(dlogits16) & 15) || (reinterpret_cast<uintptr_t>(rec) & 15))
         return SPAIR_ERR_UNSUPPORTED;
