@@ -157,6 +157,15 @@ int spair_chain_stamps(const SpairDims* d, const void* workspace, unsigned long 
 /* layout of that buffer: stamps per wavefront of the forward kernel (from offset 0; stage intervals = stamps - 1), the index of the glimpse
  * sampling interval (K4: modules.py:216-273 via models.py:387) among them, stamps per wavefront of the backward kernel (from offset 2048) */
 int spair_chain_stamp_layout(int* fwd_per_wavefront, int* fwd_glimpse_interval, int* bwd_per_wavefront);
+/* diagnostic: the kernels spair_forward / spair_backward choose for these dims, this workspace and SpairStep.flags `flags`.  Host
+ * arithmetic only (workspace is an address, never read; nothing is launched).  Writes 8 ints to host `out`: the renderer family of the
+ * forward and of the backward (SPAIR_RENDER_*), then 0/1 for: per-object records (render_prep), fp16 sprites, bf16 d-logits, the fused
+ * per-cell chain kernels, the fused decoder forward; out[7] = 0. */
+#define SPAIR_RENDER_MMA 0      /* matrix-core forward on records (render3.hip) */
+#define SPAIR_RENDER_GEN2 1     /* k_render_fwd3 / k_render_bwd2 (render2.hip) */
+#define SPAIR_RENDER_GEN1 2     /* k_render_fwd / k_render_bwd (render.hip) */
+#define SPAIR_RENDER_COLOUR 3   /* C = 2 or 3 channels (render_c.hip) */
+int spair_step_plan(const SpairDims* d, const void* workspace, int flags, int* out);
 /* wavefronts walked by the workgroup that stamps (sample 0; with the band split of grids wider than 16 cells, its top band) */
 int spair_chain_stamp_wavefronts(const SpairDims* d);
 /* band split of the fused per-cell kernels (grids wider than 16 cells: ceil(G / 8) workgroups per sample hand the boundary rows' records /

@@ -165,10 +165,10 @@ def freeze(f, *ts):
 # Spatial transformer, restated explicitly (modules.py:216-273; torch affine_grid /
 # grid_sample semantics)
 # --------------------------------------------------------------------------------------
-def _base_coords(n: int, align_corners: bool) -> torch.Tensor:
-    i = torch.arange(n, dtype=torch.float32)
+def _base_coords(n: int, align_corners: bool, dtype=torch.float32) -> torch.Tensor:
+    i = torch.arange(n, dtype=dtype)
     if align_corners:
-        return 2 * i / (n - 1) - 1 if n > 1 else torch.zeros(1)
+        return 2 * i / (n - 1) - 1 if n > 1 else torch.zeros(1, dtype=dtype)
     return (2 * i + 1) / n - 1
 
 
@@ -206,8 +206,8 @@ def stn(image: torch.Tensor, z_where: torch.Tensor, out_hw: Tuple[int, int], inv
         grid = F.affine_grid(theta, [N, C, Ho, Wo], align_corners=align_corners)
         return F.grid_sample(image, grid, padding_mode="zeros" if inverse else "border",
                              align_corners=align_corners)
-    X = _base_coords(Wo, align_corners)
-    Y = _base_coords(Ho, align_corners)
+    X = _base_coords(Wo, align_corners, image.dtype)      # float64 images: the whole sampling in float64
+    Y = _base_coords(Ho, align_corners, image.dtype)
     gx = ax[:, None] * X[None, :] + tx[:, None]            # [N,Wo]
     gy = ay[:, None] * Y[None, :] + ty[:, None]            # [N,Ho]
     ix = _unnormalize(gx, Ws, align_corners)

@@ -48,3 +48,15 @@ def ptr(t):
 
 def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+RENDER_FAMILIES = ("MMA", "GEN2", "GEN1", "COLOUR")     # SPAIR_RENDER_* (include/spair_hip.h)
+
+
+def step_plan(dims, workspace, flags=0):
+    """spair_step_plan: the kernels a step with these SpairDims, workspace address (an int; never read) and SpairStep.flags runs, as
+    {fwd, bwd: a name of RENDER_FAMILIES; rec, s16, g16, chain, dec_fused: bool}.  Host only: no GPU is needed."""
+    out = (ctypes.c_int * 8)()
+    check(lib().spair_step_plan(ctypes.byref(dims), ctypes.c_void_p(int(workspace)), int(flags), out), "spair_step_plan")
+    return dict(fwd=RENDER_FAMILIES[out[0]], bwd=RENDER_FAMILIES[out[1]], rec=bool(out[2]), s16=bool(out[3]), g16=bool(out[4]),
+                chain=bool(out[5]), dec_fused=bool(out[6]))

@@ -470,6 +470,16 @@ static void fill_diag(Ctx& c) {
     c.dstart[c.T] = n;
 }
 
+// Which kernels the step runs (host arithmetic on c.d, c.L, c.PL and c.w only): make_ctx and the spair_step_plan diagnostic
+static void plan_step(Ctx& c, int flags) {
+    const SpairDims& d = c.d;
+    c.use_chain = chain_fwd_supported(d) && !(flags & 1) && !d.obj_conv;
+    c.rg = {c.w.cb.nbox, c.w.cb.rec + (c.L.REC - 1), c.w.cb.rec + (c.L.REC - 2), c.L.ld_rec, d.B, c.L.HW, d.I, d.P, d.align_corners};
+    c.rp = render_plan(d, c.rg, c.w.ld_s, c.w.S, c.w.rrec, c.w.dLog);
+    c.use_dec_fused = c.rp.s16 /* it writes fp16 sprites */ && !(flags & 16) && c.PL.lin[LIN_DEC0].out == SP_DEC_H1 && c.PL.lin[LIN_DEC1].out == SP_DEC_H2 &&
+                      dec_fused_supported(d.A, d.P * d.P * (d.C + 1), c.L.ld_rec, c.L.N, c.w.ld_s);
+}
+
 static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
                     const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace, void* stream) {
     if (!d || !st || !params || !x || !workspace) return SPAIR_ERR_SHAPE;
@@ -489,11 +499,7 @@ static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const float
     c.w.cb.edge = params + c.PL.edge;
     c.w.cb.eps_box = eps_box; c.w.cb.eps_attr = eps_attr; c.w.cb.eps_depth = eps_depth; c.w.cb.u_pres = u_pres;
     fill_diag(c);
-    c.use_chain = chain_fwd_supported(*d) && !(st->flags & 1) && !d->obj_conv;
-    c.rg = {c.w.cb.nbox, c.w.cb.rec + (c.L.REC - 1), c.w.cb.rec + (c.L.REC - 2), c.L.ld_rec, d->B, c.L.HW, d->I, d->P, d->align_corners};
-    c.rp = render_plan(*d, c.rg, c.w.ld_s, c.w.S, c.w.rrec, c.w.dLog);
-    c.use_dec_fused = c.rp.s16 /* it writes fp16 sprites */ && !(st->flags & 16) && c.PL.lin[LIN_DEC0].out == SP_DEC_H1 && c.PL.lin[LIN_DEC1].out == SP_DEC_H2 &&
-                      dec_fused_supported(d->A, d->P * d->P * (d->C + 1), c.L.ld_rec, c.L.N, c.w.ld_s);
+    plan_step(c, st->flags);
     return SPAIR_OK;
 }
 
@@ -1567,6 +1573,23 @@ extern "C" int spair_chain_stamps(const SpairDims* d, const void* workspace, uns
     TRY(validate(*d));
     const Ws w = carve(*d, const_cast<void*>(workspace));
     if (hipMemcpyAsync(out, w.stamps, sizeof(unsigned long long) * n, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return SPAIR_ERR_LAUNCH;
+    return SPAIR_OK;
+}
+
+static_assert(SPAIR_RENDER_MMA == RENDER_MMA && SPAIR_RENDER_GEN2 == RENDER_GEN2 && SPAIR_RENDER_GEN1 == RENDER_GEN1 &&
+              SPAIR_RENDER_COLOUR == RENDER_COLOUR, "include/spair_hip.h names the RenderFamily values");
+// diagnostic: the kernel plan make_ctx computes for these dims, workspace and SpairStep.flags (host only: nothing launched, nothing read)
+extern "C" int spair_step_plan(const SpairDims* d, const void* workspace, int flags, int* out) {
+    if (!d || !workspace || !out) return SPAIR_ERR_SHAPE;
+    TRY(validate(*d));
+    Ctx c;
+    c.d = *d;
+    c.L = make_cell_layout(*d);
+    c.PL = make_param_layout(*d);
+    c.w = carve(*d, const_cast<void*>(workspace));
+    plan_step(c, flags);
+    const int v[8] = {c.rp.fwd, c.rp.bwd, c.rp.rec, c.rp.s16, c.rp.g16, c.use_chain, c.use_dec_fused, 0};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
     return SPAIR_OK;
 }
 

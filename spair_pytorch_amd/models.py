@@ -525,6 +525,12 @@ class SPAIR(nn.Module):
         torch.cuda.current_stream().synchronize()
         self._status_host[0] = 0
 
+    def step_plan(self, batch):
+        """The kernels a training step of batch size ``batch`` runs on its workspace under the current ``STEP_FLAGS`` (spair_step_plan:
+        renderer family per direction, sprite / d-logit formats, fused chain, fused decoder; see ``_lib.step_plan``)."""
+        e = self._engine(batch)
+        return L.step_plan(e["dims"], e["workspace"].data_ptr(), STEP_FLAGS)
+
     def chain_status(self):
         """Band-split hand-off status of the latest forward's workspace (grids wider than 16 cells): -1 where the chain runs unsplit, 0 = every
         hand-off arrived, 1 = a wait timed out (sticky; that step's loss and every later one is NaN).  SYNCHRONISES -- call it where the

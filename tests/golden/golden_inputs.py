@@ -23,7 +23,7 @@ def context_dim(lookback=1):
     return (2 * lookback + 1) ** 2 // 2 * (4 + N_ATTR + 1 + 1)
 
 
-def param_shapes(in_chan=1, conv_kernels=(4, 4, 4, 1, 1, 1), filters=128, lookback=1):
+def param_shapes(in_chan=1, conv_kernels=(4, 4, 4, 1, 1, 1), filters=128, lookback=1, obj_px=OBJ_PX):
     """Ordered {key: shape} for every tensor of the reference state_dict."""
     s = {}
     s["virtual_edge_element"] = (4 + N_ATTR + 2,)
@@ -53,11 +53,11 @@ def param_shapes(in_chan=1, conv_kernels=(4, 4, 4, 1, 1, 1), filters=128, lookba
     CONTEXT_DIM = context_dim(lookback)
     box_in = N_BACKBONE_FEATURES + CONTEXT_DIM
     mlp("box_network", box_in, (100, 100), (8, N_PASSTHROUGH), True)
-    mlp("object_encoder", OBJ_PX * OBJ_PX * in_chan, (256, 128), 2 * N_ATTR, False)
+    mlp("object_encoder", obj_px * obj_px * in_chan, (256, 128), 2 * N_ATTR, False)
     z_in = 4 + N_ATTR + N_PASSTHROUGH + CONTEXT_DIM + N_BACKBONE_FEATURES
     mlp("z_network", z_in, (100, 100), (2, N_PASSTHROUGH), True)
     mlp("obj_network", z_in + 1, (100, 100), 1, False)
-    mlp("object_decoder", N_ATTR, (128, 256), OBJ_PX * OBJ_PX * (in_chan + 1), False)
+    mlp("object_decoder", N_ATTR, (128, 256), obj_px * obj_px * (in_chan + 1), False)
     s["attn.gamma"] = (1,)
     for nm, o in (("query", 55 // 8), ("key", 55 // 8), ("value", 55)):
         s[f"attn.{nm}_conv.weight"] = (o, 55, 1, 1)
@@ -65,12 +65,12 @@ def param_shapes(in_chan=1, conv_kernels=(4, 4, 4, 1, 1, 1), filters=128, lookba
     return s
 
 
-def make_weights(seed, scale=1.0, in_chan=1, lookback=1):
+def make_weights(seed, scale=1.0, in_chan=1, lookback=1, obj_px=OBJ_PX):
     """U(-1/sqrt(fan_in), 1/sqrt(fan_in)) * scale per tensor (PyTorch-default-like
     magnitude), float32.  Returns {key: np.ndarray}."""
     rng = np.random.default_rng(seed)
     out = {}
-    shapes = param_shapes(in_chan, lookback=lookback)
+    shapes = param_shapes(in_chan, lookback=lookback, obj_px=obj_px)
     for key, shp in shapes.items():
         if key == "virtual_edge_element":
             t = rng.standard_normal(shp).astype(np.float32)
@@ -158,10 +158,19 @@ RGB_CASES = {
 }
 
 
+# other object sizes (config.py:33 OBJECT_SHAPE; models.py:149,387,462): the renderer's fallback families and the decoder at 36 / 64 column
+# pairs (tests/test_object_geometry_gpu.py)
+OBJ_CASES = {
+    "p24_c1_b4_step1001": dict(I=48, strides=(2, 2, 2, 1, 1, 1), B=4, step=1001, wseed=23, wscale=1.0, max_objects=3, obj_px=24),
+    "p32_i64_b2_step1": dict(I=64, strides=(2, 2, 2, 1, 1, 1), B=2, step=1, wseed=24, wscale=1.0, max_objects=4, obj_px=32),
+}
+
+
 def all_cases():
     d = dict(CASES)
     d.update(LOOKBACK_CASES)
     d.update(RGB_CASES)
+    d.update(OBJ_CASES)
     return d
 
 

@@ -32,7 +32,7 @@ REF = "/root/reference"
 SMALL = 4096  # tensors up to this many elements get their full gradient stored
 
 
-def _import_reference(I, strides, B, G, lookback=1, in_chan=1):
+def _import_reference(I, strides, B, G, lookback=1, in_chan=1, obj_px=gi.OBJ_PX):
     import matplotlib
     matplotlib.use("Agg")
     tb = types.ModuleType("tensorboardX")
@@ -52,6 +52,7 @@ def _import_reference(I, strides, B, G, lookback=1, in_chan=1):
     cfg.INPUT_IMAGE_SHAPE[:] = [in_chan, I, I]
     cfg.BATCH_SIZE = B
     cfg.N_LOOKBACK = lookback
+    cfg.OBJECT_SHAPE[:] = [obj_px, obj_px]
     for layer, s in zip(cfg.DEFAULT_BACKBONE_TOPOLOGY, strides):
         layer["stride"] = s
     from spair import models, modules, debug_tools
@@ -65,12 +66,13 @@ def run_case(name):
     in_chan = case.get("in_chan", 1)
     I, strides, B, step = case["I"], case["strides"], case["B"], case["step"]
     G = gi.grid_side(I, strides)
-    cfg, models, modules, SummaryWriter = _import_reference(I, strides, B, G, case.get("lookback", 1), in_chan)
+    obj_px = case.get("obj_px", gi.OBJ_PX)
+    cfg, models, modules, SummaryWriter = _import_reference(I, strides, B, G, case.get("lookback", 1), in_chan, obj_px)
     torch.manual_seed(3)
     with contextlib.redirect_stdout(io.StringIO()):
         m = models.SPAIR(cfg.INPUT_IMAGE_SHAPE, SummaryWriter(), torch.device("cpu"))
     assert tuple(m.feature_space_dim) == (100, G, G), m.feature_space_dim
-    w = gi.make_weights(case["wseed"], case["wscale"], in_chan=in_chan, lookback=case.get("lookback", 1))
+    w = gi.make_weights(case["wseed"], case["wscale"], in_chan=in_chan, lookback=case.get("lookback", 1), obj_px=obj_px)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in w.items()}, strict=True)
 
     x = gi.make_image(100 + case["wseed"], B, I, case["max_objects"], in_chan=in_chan)

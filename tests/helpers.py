@@ -16,11 +16,12 @@ def load_case(name):
 
 
 def oracle_cfg(case, **kw):
+    kw.setdefault("object_shape", (case.get("obj_px", gi.OBJ_PX),) * 2)
     return orc.OracleConfig(image_shape=(case.get("in_chan", 1), case["I"], case["I"]), conv_strides=tuple(case["strides"]), n_lookback=case.get("lookback", 1), **kw)
 
 
 def case_weights(case, requires_grad=False):
-    w = gi.make_weights(case["wseed"], case["wscale"], in_chan=case.get("in_chan", 1), lookback=case.get("lookback", 1))
+    w = gi.make_weights(case["wseed"], case["wscale"], in_chan=case.get("in_chan", 1), lookback=case.get("lookback", 1), obj_px=case.get("obj_px", gi.OBJ_PX))
     return {k: torch.from_numpy(v).clone().requires_grad_(requires_grad and not k.startswith("attn."))
             for k, v in w.items()}
 

@@ -9,8 +9,9 @@ from helpers import KL_NAMES, case_noise, case_weights, load_case, oracle_cfg
 from oracle import spair_oracle as orc
 
 # c4 (32x32 grid, 1024 sequential cells) is the slow one: ~1 min
-# (the N_LOOKBACK = 2 / 3 fixtures pin the generalised context gather, the rgb_* ones the C = 3 channel plumbing)
-CASES = list(gi.CASES) + list(gi.LOOKBACK_CASES) + list(gi.RGB_CASES)
+# (the N_LOOKBACK = 2 / 3 fixtures pin the generalised context gather, the rgb_* ones the C = 3 channel plumbing, the p* ones object sizes
+# other than 28 px)
+CASES = list(gi.CASES) + list(gi.LOOKBACK_CASES) + list(gi.RGB_CASES) + list(gi.OBJ_CASES)
 
 
 def rel(a, b):
@@ -88,6 +89,40 @@ def test_units_stn_and_decay(golden_dir):
     for s, wv, cv in zip(u["decay_steps"], u["decay_wheel"], u["decay_count_log"]):
         assert float(orc.exponential_decay(int(s), **c.wheel)) == float(wv)
         assert float(orc.exponential_decay(int(s), **c.count_prior)) == float(cv)
+
+
+@pytest.mark.parametrize("align_corners", [False, True])
+@pytest.mark.parametrize("P,I", [(28, 64), (24, 48), (32, 72), (25, 80)])
+def test_explicit_stn_matches_float64_grid_sample(P, I, align_corners):
+    """The oracle's explicit spatial transformer (fast=False: what the GPU tests compare against) against torch's affine_grid +
+    grid_sample in float64, values and gradients, both directions: glimpse (border padding, clipped coordinates included) and inverse
+    (zeros padding, closed-form inverse).  align_corners = True cannot come from the reference (its grid_sample calls take torch's
+    default), so this anchors the oracle there."""
+    import torch.nn.functional as F
+    g = torch.Generator().manual_seed(P * 1000 + I + int(align_corners))
+    n, C = 8, 2
+    zw = torch.stack([torch.rand(n, generator=g) * 1.6 - 0.3, torch.rand(n, generator=g) * 1.6 - 0.3,
+                      torch.rand(n, generator=g) * 1.2 + 0.05, torch.rand(n, generator=g) * 1.2 + 0.05], 1).double()
+    for inverse in (False, True):
+        src = torch.rand(n, C, *((P, P) if inverse else (I, I)), generator=g, dtype=torch.float64)
+        out_hw = (I, I) if inverse else (P, P)
+        a_src, a_zw = src.clone().requires_grad_(True), zw.clone().requires_grad_(True)
+        out = orc.stn(a_src, a_zw, out_hw, inverse=inverse, align_corners=align_corners, inverse_mode="closed")
+        b_src, b_zw = src.clone().requires_grad_(True), zw.clone().requires_grad_(True)
+        xt, yt, xs, ys = b_zw.unbind(-1)
+        tx, ty, z = 2 * xt - 1, 2 * yt - 1, torch.zeros_like(xs)
+        rows = ((1 / xs, z, -tx / xs), (z, 1 / ys, -ty / ys)) if inverse else ((xs, z, tx), (z, ys, ty))
+        theta = torch.stack([torch.stack(r, -1) for r in rows], 1)
+        grid = F.affine_grid(theta, [n, C, *out_hw], align_corners=align_corners)
+        want = F.grid_sample(b_src, grid, padding_mode="zeros" if inverse else "border", align_corners=align_corners)
+        assert (out - want).abs().max().item() < 1e-6, inverse
+        gw = torch.randn(want.shape, generator=g, dtype=torch.float64)
+        (out * gw).sum().backward()
+        (want * gw).sum().backward()
+        assert (a_src.grad - b_src.grad).abs().max().item() <= 1e-6 * b_src.grad.abs().max().item(), inverse
+        assert (a_zw.grad - b_zw.grad).abs().max().item() <= 1e-5 * b_zw.grad.abs().max().item(), inverse
+        if not inverse:      # some glimpses reach past the image: the clip (zero gradient) is exercised
+            assert ((zw[:, 0] * 2 - 1 + zw[:, 2]) > 1).any() or ((zw[:, 0] * 2 - 1 - zw[:, 2]) < -1).any()
 
 
 def test_backbone_geometry_known_answers():
