@@ -133,6 +133,21 @@ int spair_backward_out(const SpairDims* d, const SpairStep* st, const float* par
                        void* ev_decoder, void* ev_cells, void* ev_backbone,
                        const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
                        float* aux_scratch);
+/* spair_backward_x: spair_backward_out that also writes the gradient of the step with respect to its input image into grad_x [B,C,I,I]
+ * (OVERWRITTEN, fp32): the backbone term (the stem's data gradient from d act0), the glimpse term (the adjoint of the border-padded STN
+ * glimpse) and, with bce_target != 0, the BCE-target term *grad_loss * (log1p(-recon) - log(recon)) -- torch's gradient of
+ * binary_cross_entropy with respect to its target, not clamped: +inf where recon == 0, -inf where recon == 1 (the status word is not
+ * affected).  bce_target = 0 is for a backward through the outputs alone, where the loss is not part of the graph.  These kernels run
+ * after ev_backbone is recorded.  x_scratch: spair_input_grad_scratch_bytes(d) bytes.  grad_x == NULL is spair_backward_out, kernel for
+ * kernel.  No atomics on grad_x: deterministic. */
+int spair_backward_x(const SpairDims* d, const SpairStep* st, const float* params, const float* x,
+                     const float* eps_box, const float* eps_attr, const float* eps_depth, const float* u_pres,
+                     void* workspace, const float* grad_loss, float* grads, void* stream,
+                     void* ev_decoder, void* ev_cells, void* ev_backbone,
+                     const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
+                     float* aux_scratch, float* grad_x, int bce_target, void* x_scratch);
+/* host arithmetic only: bytes of spair_backward_x's x_scratch (-1 for invalid dims); never part of spair_workspace_bytes */
+int64_t spair_input_grad_scratch_bytes(const SpairDims* d);
 /* torch.optim.Adam(lr) defaults (train.py:44) on flat buffers, one launch. */
 int spair_adam(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                float beta1, float beta2, float eps, int step, void* stream);
@@ -257,6 +272,15 @@ int spair_stn_glimpse_fwd(const float* x, const float* nbox, int B, float* glimp
                           int I, int P, int align_corners, void* stream);
 int spair_stn_glimpse_bwd(const float* x, const float* nbox, int B, const float* dglimpse, int ld_gl,
                           float* dnbox, int R, int C, int I, int P, int align_corners, void* stream);
+/* The two kernels of spair_backward_x's image gradient on their own (csrc/input_grad.hip).
+ * spair_input_grad_glimpse: adjoint of spair_stn_glimpse_fwd with respect to the IMAGE.  Rows r = k*B + b (k < ncell) of dglimpse
+ * [rows][ld_gl] ((c, i, j) order) and nbox [rows][4]; out [B,C,I,I] = sum over k of sample b's rows, overwritten, deterministic.
+ * spair_input_grad_stem: data gradient of the stem conv (weights w [Cout,C,k,k], stride s) from dact0 [B,Hout,Hout,Cout] (fp32, or bf16 with
+ * dact_bf16), cropped by pad_pre to grad_x [B,C,I,I] (overwritten) and plus add [B,C,I,I] (NULL = none). */
+int spair_input_grad_glimpse(const float* nbox, int B, int ncell, const float* dglimpse, int ld_gl, float* out, int C, int I, int P,
+                             int align_corners, void* stream);
+int spair_input_grad_stem(const void* dact0, int dact_bf16, const float* w, int B, int C, int I, int pad_pre, int k, int s, int Hout,
+                          int Cout, const float* add, float* grad_x, void* stream);
 /* stn(sprites, z_where, [I,I], inverse=True) materialised (modules.py:256-269): sprites [N,C,P,P] -> out [N,C,I,I], bilinear, zeros
  * padding, inverse affine in closed form; backward ACCUMULATES into dsprites [N,C,P,P] and dnbox [N,4] (zero them first).  Only for
  * callers of the reference's helper -- the training step never materialises this tensor (spair_render_fwd fuses it). */

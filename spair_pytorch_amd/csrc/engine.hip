@@ -400,6 +400,7 @@ struct Ctx {
     RenderGeom rg;         // the renderer's objects: the rows' nbox, presence and depth
     RenderPlan rp;         // the renderer's kernels and sprite / d-logit formats (render.h)
     float* tn_scratch = nullptr;   // split-K scratch override while work is being issued on the helper stream
+    bool keep_dact0 = false;       // spair_backward_x: d act0 goes to HBM (the stem's data gradient reads it), no stem fusion into conv_1
     std::vector<int> dstart;
 };
 
@@ -810,7 +811,8 @@ static int backbone_bwd16(Ctx& c, float* grads) {
             if (cs.k == 4 && cs.s == 2 && cs.cin == 128 && cs.cout == 128 && cs.hin == 2 * (cs.hout + 1) && !(c.st.flags & 32)) {
                 // patch-resident data gradient (conv_s2_dgrad.hip): the d-out neighbourhood of a tile is staged once for all 4 parity classes x 4 taps
                 const ConvSpec& c0 = c.PL.conv[0];
-                const bool want_stem = i == 1 && c0.cin == 1 && c0.k == 4 && c0.cout == 128 && c0.hout == cs.hin && !(c.st.flags & 8);
+                const bool want_stem = i == 1 && c0.cin == 1 && c0.k == 4 && c0.cout == 128 && c0.hout == cs.hin && !(c.st.flags & 8) &&
+                                       !c.keep_dact0;
                 const void* wd4[4] = {c.w.conv_wd[i][0], c.w.conv_wd[i][1], c.w.conv_wd[i][2], c.w.conv_wd[i][3]};
                 // conv_1's gate as the stem kernel's sign bits (20 MB instead of the 321-MB activation) whenever that kernel wrote them
                 const void* gbits = nullptr;
@@ -850,7 +852,7 @@ static int backbone_bwd16(Ctx& c, float* grads) {
                     const ConvSpec& c0 = c.PL.conv[0];
                     g.stem_xp = c.w.xpad; g.stem_hin = c0.hin; g.stem_s = c0.s; g.stem_dw = grads + c0.w; g.stem_db = grads + c0.b;
                     g.stem_part = c.w.tn_part; g.stem_part_cap = SPAIR_TN_PART_FLOATS;
-                    stem_fused = c0.cin == 1 && c0.k == 4 && c0.cout == 128 && c0.hout == cs.hin && !(c.st.flags & 8) &&
+                    stem_fused = c0.cin == 1 && c0.k == 4 && c0.cout == 128 && c0.hout == cs.hin && !(c.st.flags & 8) && !c.keep_dact0 &&
                                  spair_nt16_stem_fusable(g, g.stem_part_cap);
                     if (!stem_fused) g.stem_part = nullptr;
                 }
@@ -1372,15 +1374,29 @@ extern "C" int spair_backward_ev(const SpairDims* d, const SpairStep* st, const 
                               ev_backbone, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
-extern "C" int spair_backward_out(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
-                                  const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace,
-                                  const float* grad_loss, float* grads, void* stream, void* ev_decoder, void* ev_cells, void* ev_backbone,
-                                  const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
-                                  float* aux_scratch) {
+int input_grad_glimpse(const float* nbox, int B, int ncell, const float* dgl, int ld, float* out, int C, int I, int P, int ac, hipStream_t s);
+int input_grad_stem(const void* dact, int dact_bf16, const float* w, int B, int C, int I, int pre, int k, int s, int Hout, int Cout,
+                    const float* add, const float* aux, const float* bce_g, float* grad_x, hipStream_t st);
+
+extern "C" int64_t spair_input_grad_scratch_bytes(const SpairDims* d) {
+    if (!d || validate(*d) != SPAIR_OK) return -1;
+    return ((int64_t)d->B * d->C * d->I * d->I * 4 + 255) & ~(int64_t)255;      // dx_gl [B][C][I][I] fp32
+}
+
+// grad_x == nullptr: exactly spair_backward_out.  Otherwise, once the parameter gradients are complete (after ev_backbone), the image
+// gradient: [chain] dGl = dHe1 W_enc0, the glimpse adjoint into x_scratch, then the stem's data gradient, whose epilogue writes grad_x
+static int backward_impl(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
+                         const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace,
+                         const float* grad_loss, float* grads, void* stream, void* ev_decoder, void* ev_cells, void* ev_backbone,
+                         const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
+                         float* aux_scratch, float* grad_x, int bce_target, float* x_scratch) {
     Ctx c;
     TRY(make_ctx(c, d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, stream));
     if (!grad_loss || !grads) return SPAIR_ERR_SHAPE;
     if (grad_recon && (!inv_den || !aux_scratch)) return SPAIR_ERR_SHAPE;
+    if (grad_x && (!x_scratch || c.PL.n_conv < 2)) return grad_x && !x_scratch ? SPAIR_ERR_SHAPE : SPAIR_ERR_UNSUPPORTED;
+    if (grad_x && (size_t)c.PL.conv[0].cout * d->C * c.PL.conv[0].k * c.PL.conv[0].k * 4 > 65536) return SPAIR_ERR_UNSUPPORTED;
+    c.keep_dact0 = grad_x != nullptr;
     const CellLayout& L = c.L;
     CellBufs& P = c.w.cb;
     const ParamLayout& PL = c.PL;
@@ -1564,7 +1580,37 @@ extern "C" int spair_backward_out(const SpairDims* d, const SpairStep* st, const
     { ProfScope ps(PS_BACKBONE_BWD, c.s); TRY(backbone_bwd(c, grads)); }
     if (side && hipStreamWaitEvent(main_s, side->ev[3], 0) != hipSuccess) return SPAIR_ERR_LAUNCH;      // join
     TRY(record_ready(ev_backbone, main_s));
+    if (grad_x) {     // behind ev_backbone: the gradient buckets are not delayed
+        if (c.use_chain) {      // the fused chain keeps dHe1 (bf16) but not dGl: one 16-bit NT GEMM, as bwd_lin does per wavefront
+            const LinSpec& e0 = PL.lin[LIN_ENC0];
+            const int K = round_up(e0.out, 8);
+            TRY(nt16(c, P.dHe1, SP_ENC_H1, c.w.lin_wt[LIN_ENC0], K, P.dGl, L.ld_gl, 0, N, e0.in, K, nullptr, nullptr, 0, 0));
+        }
+        TRY(input_grad_glimpse(P.nbox, d->B, d->G * d->G, P.dGl, L.ld_gl, x_scratch, d->C, d->I, d->P, d->align_corners, main_s));
+        const ConvSpec& c0 = PL.conv[0];
+        TRY(input_grad_stem(c.w.dact[0], b16, params + c0.w, d->B, d->C, d->I, d->pad_pre, c0.k, c0.s, c0.hout, c0.cout, x_scratch, c.w.aux,
+                            bce_target ? grad_loss : nullptr, grad_x, main_s));
+    }
     return SPAIR_OK;
+}
+
+extern "C" int spair_backward_out(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
+                                  const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace,
+                                  const float* grad_loss, float* grads, void* stream, void* ev_decoder, void* ev_cells, void* ev_backbone,
+                                  const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
+                                  float* aux_scratch) {
+    return backward_impl(d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, grad_loss, grads, stream, ev_decoder, ev_cells,
+                         ev_backbone, inv_den, grad_recon, grad_z_where, grad_z_pres, aux_scratch, nullptr, 0, nullptr);
+}
+
+extern "C" int spair_backward_x(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
+                                const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace,
+                                const float* grad_loss, float* grads, void* stream, void* ev_decoder, void* ev_cells, void* ev_backbone,
+                                const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
+                                float* aux_scratch, float* grad_x, int bce_target, void* x_scratch) {
+    return backward_impl(d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, grad_loss, grads, stream, ev_decoder, ev_cells,
+                         ev_backbone, inv_den, grad_recon, grad_z_where, grad_z_pres, aux_scratch, grad_x, bce_target,
+                         reinterpret_cast<float*>(x_scratch));
 }
 
 // diagnostic: copy the forward chain kernel's stage stamps (SpairStep.flags bit 1) into a caller buffer of n uint64

@@ -14,6 +14,9 @@ step, train.py:64-67) runs unchanged.  All arithmetic of the step is in libspair
 * with ``differentiable_outputs=True`` the recon / z_where / z_pres outputs are autograd tensors
   too, as in the reference: adjoints that reach them are folded into that same reverse pass
   (``spair_forward_out`` / ``spair_backward_out``);
+* an input ``x`` that requires grad gets the reference's ``x.grad`` (``spair_backward_x``): the
+  backbone, glimpse and BCE-target terms.  As in torch, the BCE-target term is ``-logit(recon)``
+  unclamped: ``x.grad`` is +inf wherever recon is exactly 0 (-inf where it is exactly 1);
 * there is no PyTorch/CPU fallback: without the HIP library or a GPU this module raises.
 """
 import ctypes
@@ -119,7 +122,8 @@ class _StepFn(torch.autograd.Function):
     the parameter gradients are accumulated straight into the flat gradient buffer (the views
     behind every ``p.grad``) by ``spair_backward`` instead of being returned one tensor at a time.
     recon / z_where / z_pres are differentiable only with ``model.differentiable_outputs``; their
-    adjoints then enter the same reverse pass (``spair_backward_out``)."""
+    adjoints then enter the same reverse pass (``spair_backward_out``).  When ``x`` requires grad
+    the same pass also returns its gradient (``spair_backward_x``)."""
 
     @staticmethod
     def forward(ctx, anchor, model, x, step, noise):
@@ -151,11 +155,15 @@ class _StepFn(torch.autograd.Function):
                 "backward() of a SPAIR forward whose saved activations were overwritten by a later forward of the same batch size, or "
                 "whose workspace the engine cache has dropped (the engine keeps ONE set of activations per batch size and "
                 "`max_engines` batch sizes; call backward before the next forward of that size)")
-        if g_loss is None:        # a backward through the outputs alone: the loss terms (KL scale included) get a zero adjoint
+        # a backward through the outputs alone: the loss terms (KL scale included) get a zero adjoint, and the loss's BCE-target term
+        # is left out of x's gradient (as in torch, where the loss is then not part of the graph: no 0 * inf)
+        bce_target = g_loss is not None
+        if g_loss is None:
             g_loss = torch.zeros((), device=ctx.x.device, dtype=torch.float32)
         outs = [None if g is None else g.contiguous().float() for g in (g_recon, g_zw, g_zp)]
-        ctx.model._run_backward(ctx.x, ctx.step, ctx.noise, g_loss.contiguous().float(), engine, *outs)
-        return None, None, None, None, None      # the parameter gradients went straight into the flat buffer
+        grad_x = torch.empty_like(ctx.x) if ctx.needs_input_grad[2] else None
+        ctx.model._run_backward(ctx.x, ctx.step, ctx.noise, g_loss.contiguous().float(), engine, *outs, grad_x=grad_x, bce_target=bce_target)
+        return None, None, grad_x, None, None      # the parameter gradients went straight into the flat buffer
 
 
 class SPAIR(nn.Module):
@@ -394,6 +402,18 @@ class SPAIR(nn.Module):
             e["aux_scratch"] = torch.empty(2 * d.B * d.C * d.I * d.I + 1, device=self.device, dtype=torch.float32)
         return e["inv_den"], e["aux_scratch"]
 
+    def _input_grad_scratch(self, e):
+        """Scratch of the image gradient of engine ``e`` (the glimpse term, [B,C,I,I] fp32), allocated on first use; never part of the
+        workspace."""
+        if e.get("x_scratch") is None:
+            lib = L.lib()
+            lib.spair_input_grad_scratch_bytes.restype = ctypes.c_int64
+            nbytes = lib.spair_input_grad_scratch_bytes(ctypes.byref(e['dims']))
+            if nbytes <= 0:
+                raise L.SpairHipError("spair_input_grad_scratch_bytes refused these dims")
+            e["x_scratch"] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return e["x_scratch"]
+
     def _draw_noise(self, e):
         """The 7 per-cell draws (models.py:333-336,84,95,402-403) as whole maps, one launch; the seed
         comes from torch's CPU generator so torch.manual_seed controls it."""
@@ -424,26 +444,32 @@ class SPAIR(nn.Module):
                                           L.stream(), L.ptr(inv_den)), "spair_forward")
         return loss_terms, recon, z_where, z_pres
 
-    def _run_backward(self, x, step, noise, g_loss, e=None, g_recon=None, g_z_where=None, g_z_pres=None):
-        """``g_recon`` / ``g_z_where`` / ``g_z_pres``: contiguous fp32 adjoints of the forward's outputs, or None (nothing launched for them)."""
+    def _run_backward(self, x, step, noise, g_loss, e=None, g_recon=None, g_z_where=None, g_z_pres=None, grad_x=None, bce_target=True):
+        """``g_recon`` / ``g_z_where`` / ``g_z_pres``: contiguous fp32 adjoints of the forward's outputs, or None (nothing launched for them).
+        ``grad_x``: a contiguous fp32 tensor shaped like ``x`` that receives the image gradient (overwritten), or None (spair_backward_out);
+        ``bce_target``: include the loss's BCE-target term in it."""
         e = e if e is not None else self._engine(x.shape[0])
         st = step_scalars(step, x.shape[0], self.world_size, True)
         self._bind_grads()
         gb = self._grad_buckets
         ev = gb.handles() if gb is not None else [ctypes.c_void_p(0)] * 3
-        L.check(L.lib().spair_backward_out(ctypes.byref(e['dims']), ctypes.byref(st), L.ptr(self._flat), L.ptr(x), L.ptr(noise['eps_box']),
-                                           L.ptr(noise['eps_attr']), L.ptr(noise['eps_depth']), L.ptr(noise['u_pres']),
-                                           L.ptr(e['workspace']), L.ptr(g_loss), L.ptr(self._flat_grad), L.stream(), ev[0], ev[1], ev[2],
-                                           L.ptr(e.get('inv_den')), L.ptr(g_recon), L.ptr(g_z_where), L.ptr(g_z_pres),
-                                           L.ptr(e.get('aux_scratch'))),
-                "spair_backward")
+        args = (ctypes.byref(e['dims']), ctypes.byref(st), L.ptr(self._flat), L.ptr(x), L.ptr(noise['eps_box']), L.ptr(noise['eps_attr']),
+                L.ptr(noise['eps_depth']), L.ptr(noise['u_pres']), L.ptr(e['workspace']), L.ptr(g_loss), L.ptr(self._flat_grad), L.stream(),
+                ev[0], ev[1], ev[2], L.ptr(e.get('inv_den')), L.ptr(g_recon), L.ptr(g_z_where), L.ptr(g_z_pres), L.ptr(e.get('aux_scratch')))
+        if grad_x is None:
+            L.check(L.lib().spair_backward_out(*args), "spair_backward")
+        else:
+            L.check(L.lib().spair_backward_x(*args, L.ptr(grad_x), ctypes.c_int(int(bool(bce_target))), L.ptr(self._input_grad_scratch(e))),
+                    "spair_backward_x")
         if gb is not None:
             gb.pending = True             # ddp.allreduce_gradients(model) consumes the three events
 
     # ---- public API ------------------------------------------------------------------------------------
     def forward(self, x, global_step=0, noise=None):
         """models.py:35-131.  ``noise`` (optional dict eps_box/eps_attr/eps_depth/u_pres, NCHW maps)
-        replaces the internal draws -- used by the parity tests."""
+        replaces the internal draws -- used by the parity tests.  An ``x`` that requires grad gets the reference's gradient on backward;
+        it is +inf wherever recon is exactly 0 (-inf where exactly 1): torch's BCE gradient with respect to its target is -logit(recon),
+        unclamped, and this keeps it."""
         self._ensure_ready()
         if not x.is_cuda:
             raise L.SpairHipError("input must be on the MI355X (got %s); there is no CPU path" % x.device)
