@@ -65,7 +65,8 @@ typedef struct SpairStep {
     float count_prior_prob;    /* 1/(1+exp(-log(v+1e-6))), models.py:186-188 */
     float kl_scale;            /* 1/(B*world_size): batch-mean of the KL terms (models.py:553) */
     int train;                 /* 1: keep what backward needs */
-    int flags;                 /* bit 0: disable the fused persistent per-cell kernels (A/B testing); bit 1: record stage stamps;
+    int flags;                 /* bits 0 and 2-6 are inputs of the step's kernel plan (spair_step_plan_n); bit 1 is not.
+                                * bit 0: disable the fused persistent per-cell kernels (A/B testing); bit 1: record stage stamps;
                                 * bit 2: no helper stream (every kernel on the caller's stream);
                                 * bit 3: stem weight gradient as its own kernel (not fused into conv_1's data gradient);
                                 * bit 4: decoder forward as three GEMM launches instead of the fused activation-stationary kernel;
@@ -172,14 +173,34 @@ int spair_chain_stamps(const SpairDims* d, const void* workspace, unsigned long 
 /* layout of that buffer: stamps per wavefront of the forward kernel (from offset 0; stage intervals = stamps - 1), the index of the glimpse
  * sampling interval (K4: modules.py:216-273 via models.py:387) among them, stamps per wavefront of the backward kernel (from offset 2048) */
 int spair_chain_stamp_layout(int* fwd_per_wavefront, int* fwd_glimpse_interval, int* bwd_per_wavefront);
-/* diagnostic: the kernels spair_forward / spair_backward choose for these dims, this workspace and SpairStep.flags `flags`.  Host
- * arithmetic only (workspace is an address, never read; nothing is launched).  Writes 8 ints to host `out`: the renderer family of the
- * forward and of the backward (SPAIR_RENDER_*), then 0/1 for: per-object records (render_prep), fp16 sprites, bf16 d-logits, the fused
- * per-cell chain kernels, the fused decoder forward; out[7] = 0. */
+/* diagnostic: the kernels spair_forward / spair_backward choose for these dims, this workspace, SpairStep.flags `flags` and, for the
+ * backward, whether an image gradient is requested (input_grad: spair_backward_x with grad_x).  Host arithmetic only (workspace is an address,
+ * never read; nothing is launched).  Writes the first min(n, SPAIR_STEP_PLAN_INTS) of these ints to host `out`:
+ *   [0..7]   the renderer family of the forward and of the backward (SPAIR_RENDER_*), then 0/1 for: per-object records (render_prep), fp16
+ *            sprites, bf16 d-logits, the fused per-cell chain kernels, the fused decoder forward; out[7] = 0;
+ *   [8..11]  0/1 for: the helper stream, the decoder's data gradients in one launch, its two small weight gradients in one grouped launch,
+ *            its weight gradients issued behind the chain backward (the last three: bf16 step, MLP decoder);
+ *   [12]     the first backbone layer of the fused trailing 1x1 stack (layer 0 is the stem, conv_out is layer n_conv; n_conv + 1: none);
+ *   [13]     where the stem's weight gradient is taken (SPAIR_STEM_*);
+ *   [14..21] per backbone layer 1 .. 8 (conv_out included) the forward kernel (SPAIR_CONV_*), -1 past conv_out;
+ *   [22..29] the same for its data gradient;
+ *   [30..37] 0/1: the layer's data gradient reads its ReLU gate as the sign bits the forward of the layer below left (else the stored
+ *            activation), -1 past conv_out. */
+#define SPAIR_STEP_PLAN_INTS 38
 #define SPAIR_RENDER_MMA 0      /* matrix-core forward on records (render3.hip) */
 #define SPAIR_RENDER_GEN2 1     /* k_render_fwd3 / k_render_bwd2 (render2.hip) */
 #define SPAIR_RENDER_GEN1 2     /* k_render_fwd / k_render_bwd (render.hip) */
 #define SPAIR_RENDER_COLOUR 3   /* C = 2 or 3 channels (render_c.hip) */
+#define SPAIR_CONV_GEMM 0       /* one implicit-GEMM launch in the step's dtype (a strided data gradient: all output-parity classes in it) */
+#define SPAIR_CONV_PATCH 1      /* the patch-resident kernel of 128 -> 128 channel 4x4 / stride-2 layers (conv_s2.hip, conv_s2_dgrad.hip) */
+#define SPAIR_CONV_PER_CLASS 2  /* one implicit-GEMM launch per output-parity class */
+#define SPAIR_CONV_PW_STACK 3   /* the fused trailing stack of 1x1 layers (pointwise.hip) */
+#define SPAIR_STEM_PATCH 0      /* fused into conv_1's patch-resident data gradient */
+#define SPAIR_STEM_GEMM 1       /* fused into the epilogue of conv_1's implicit-GEMM data gradient */
+#define SPAIR_STEM_WGRAD16 2    /* its own kernel (grey-scale 4x4 stem, bf16 step) */
+#define SPAIR_STEM_GENERIC 3    /* the TN GEMM (fp32 step, other stems) */
+int spair_step_plan_n(const SpairDims* d, const void* workspace, int flags, int input_grad, int* out, int n);
+/* the first 8 ints of spair_step_plan_n without an image gradient */
 int spair_step_plan(const SpairDims* d, const void* workspace, int flags, int* out);
 /* wavefronts walked by the workgroup that stamps (sample 0; with the band split of grids wider than 16 cells, its top band) */
 int spair_chain_stamp_wavefronts(const SpairDims* d);

@@ -60,3 +60,22 @@ def step_plan(dims, workspace, flags=0):
     check(lib().spair_step_plan(ctypes.byref(dims), ctypes.c_void_p(int(workspace)), int(flags), out), "spair_step_plan")
     return dict(fwd=RENDER_FAMILIES[out[0]], bwd=RENDER_FAMILIES[out[1]], rec=bool(out[2]), s16=bool(out[3]), g16=bool(out[4]),
                 chain=bool(out[5]), dec_fused=bool(out[6]))
+
+
+CONV_KERNELS = ("GEMM", "PATCH", "PER_CLASS", "PW_STACK")      # SPAIR_CONV_*
+STEM_WGRADS = ("PATCH", "GEMM", "WGRAD16", "GENERIC")          # SPAIR_STEM_*
+STEP_PLAN_INTS = 38                                            # SPAIR_STEP_PLAN_INTS
+
+
+def step_plan_n(dims, workspace, flags=0, input_grad=False):
+    """spair_step_plan_n: the rest of the plan step_plan reports, for a step with these SpairDims, workspace address, SpairStep.flags and
+    (backward) image gradient, as {side, dec_dgrad_fused, dec_wgrad_grouped, dec_wgrad_late: bool; pw0: first layer of the fused 1x1 stack
+    (n_conv + 1: none); stem: where the stem's weight gradient is taken, a name of STEM_WGRADS; fwd, dgrad: per backbone layer 1 .. n_conv
+    (conv_out last) a name of CONV_KERNELS; gate_bits: per layer, whether its data gradient reads the sign bits the layer below left}."""
+    out = (ctypes.c_int * STEP_PLAN_INTS)()
+    check(lib().spair_step_plan_n(ctypes.byref(dims), ctypes.c_void_p(int(workspace)), int(flags), int(bool(input_grad)), out, STEP_PLAN_INTS),
+          "spair_step_plan_n")
+    layers = range(dims.n_conv)
+    return dict(side=bool(out[8]), dec_dgrad_fused=bool(out[9]), dec_wgrad_grouped=bool(out[10]), dec_wgrad_late=bool(out[11]), pw0=out[12],
+                stem=STEM_WGRADS[out[13]], fwd=tuple(CONV_KERNELS[out[14 + i]] for i in layers),
+                dgrad=tuple(CONV_KERNELS[out[22 + i]] for i in layers), gate_bits=tuple(bool(out[30 + i]) for i in layers))

@@ -15,7 +15,7 @@
 // by LDS-DMA (buffer_load ... lds, XOR swizzle applied on the source side) behind counted s_waitcnt vmcnt; the two wave groups of a workgroup
 // alternate between a fragment-load phase and an MFMA phase (ping-pong, see the kernel).
 #include "common.h"
-#include "gemm.h"
+#include "backbone.h"
 
 namespace {
 
@@ -201,8 +201,8 @@ __global__ __launch_bounds__(768, 3) void k_conv_s2k4_patch(ConvPatchArgs a) {
 }  // namespace
 
 // in: bf16 NHWC [B][Hin][Hin][128]; wf: bf16 [128][2048] in tap-parity K order (engine.hip fill_ktab / k_prep mode 2 with T, s set);
-// out: bf16 [B*Hout*Hout][128] = relu(conv + bias).  SPAIR_ERR_UNSUPPORTED: the caller keeps the implicit-GEMM kernel.
-// geometry check shared by the launcher and by conv_s2k4_patch_fwd16_fits(): SPAIR_OK with the tiling, or SPAIR_ERR_UNSUPPORTED
+// out: bf16 [B*Hout*Hout][128] = relu(conv + bias).
+// geometry check shared by the launcher and by conv_s2k4_patch_fwd16_supported(): SPAIR_OK with the tiling, or SPAIR_ERR_UNSUPPORTED
 static int cp_plan(int B, int Hin, int Hout, int cin, int cout, int k, int s_, int& tiles_out, int& tpi_out) {
     if (cin != CP_C || cout != CP_C || k != 4 || s_ != 2 || Hin != 2 * Hout + 2 || B <= 0 || Hout <= 0) return SPAIR_ERR_UNSUPPORTED;
     const long long M = (long long)B * Hout * Hout;
@@ -232,8 +232,7 @@ static int cp_plan(int B, int Hin, int Hout, int cin, int cout, int k, int s_, i
     tiles_out = tiles; tpi_out = tpi;
     return SPAIR_OK;
 }
-// does the patch-resident kernel take this layer (then it also leaves the sign-bit mask the next layer's data gradient reads)?
-bool conv_s2k4_patch_fwd16_fits(int B, int Hin, int Hout, int cin, int cout, int k, int s_) {
+bool conv_s2k4_patch_fwd16_supported(int B, int Hin, int Hout, int cin, int cout, int k, int s_) {
     int t, p;
     return cp_plan(B, Hin, Hout, cin, cout, k, s_, t, p) == SPAIR_OK;
 }

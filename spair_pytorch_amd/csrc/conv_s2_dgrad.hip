@@ -15,7 +15,7 @@
 // layer below > 0), then either the row-mapped store of d act or (STEM) the gated tile x the 4x4 input patches on the matrix cores, summed
 // over the tile's 4 classes and left as ONE [128][17] partial per workgroup.
 #include "common.h"
-#include "gemm.h"
+#include "backbone.h"
 
 namespace {
 
@@ -351,17 +351,14 @@ __global__ __launch_bounds__(768, 3) void k_conv_s2k4_dgrad(ConvDgradArgs a) {
 
 int spair_stem_fused_reduce(float* part, int nblk, float* dw, float* db, hipStream_t s);      // gemm16.hip
 
-// dout: bf16 NHWC [B][Ho][Ho][128]; wd[q]: bf16 [128 ci][4 taps * 128 co] of output-parity class q = py * 2 + px (k_prep mode 3); gate: the
-// stored activation of the layer below, bf16 NHWC [B][2 (Ho + 1)][2 (Ho + 1)][128]; out: d of that activation (same layout), or -- when
-// stem_part != nullptr -- nothing: the stem's weight / bias gradient is accumulated into stem_dw [128][16] / stem_db [128] instead.
-// SPAIR_ERR_UNSUPPORTED: the caller keeps the implicit-GEMM kernel.
-int conv_s2k4_patch_dgrad16(const void* dout, const void* const* wd, const void* gate, void* out, int B, int Ho, int hin, int cin, int cout, int k,
-                            int s_, const float* stem_xp, int stem_hin, int stem_s, float* stem_part, long long stem_part_cap, float* stem_dw,
-                            float* stem_db, hipStream_t s, const void* gate_bits) {
+// geometry and scratch check shared by the launcher and the _supported predicates: the tiling (tpi: tiles per image, 0 = whole-batch tiles) and
+// the persistent grid, or false.  stem: one [128][17] partial per workgroup in stem_part_cap floats, an even stem input side and stride.
+static bool dg_plan(int B, int Ho, int hin, int cin, int cout, int k, int s_, bool stem, int stem_hin, int stem_s, long long stem_part_cap,
+                    int& tpi_out, int& grid_out) {
     const int Hc = Ho + 1;
-    if (cin != DG_C || cout != DG_C || k != 4 || s_ != 2 || hin != 2 * Hc || B <= 0 || Ho <= 0) return SPAIR_ERR_UNSUPPORTED;
+    if (cin != DG_C || cout != DG_C || k != 4 || s_ != 2 || hin != 2 * Hc || B <= 0 || Ho <= 0) return false;
     const long long M = (long long)B * Hc * Hc;
-    if ((long long)B * hin * hin * DG_C >= (1ll << 31)) return SPAIR_ERR_UNSUPPORTED;
+    if ((long long)B * hin * hin * DG_C >= (1ll << 31)) return false;
     auto window = [&](long long m0, long long ml) {
         const long long g0 = m0 / Hc, g1 = ml / Hc;
         return (int)((g1 + g1 / Hc + 1) * (Ho + 2) + (ml - g1 * Hc) + 1 - ((g0 + g0 / Hc) * (Ho + 2) + (m0 - g0 * Hc)) + 1);
@@ -378,14 +375,35 @@ int conv_s2k4_patch_dgrad16(const void* dout, const void* const* wd, const void*
         tpi = (HH + DG_BM - 1) / DG_BM;
         worst = 0;
         for (int t = 0; t < tpi; ++t) worst = std::max(worst, window((long long)t * DG_BM, std::min<long long>((long long)(t + 1) * DG_BM, HH) - 1));
-        if (worst > DG_PPX) return SPAIR_ERR_UNSUPPORTED;
+        if (worst > DG_PPX) return false;
         tiles = B * tpi;
     }
+    const int grid = std::min(tiles, spair_num_cus());      // persistent: one 160-KB workgroup per CU walks the tiles
+    if (stem && ((long long)grid * DG_STEM_FLOATS > stem_part_cap || (stem_hin & 1) || (stem_s & 1))) return false;
+    tpi_out = tpi; grid_out = grid;
+    return true;
+}
+bool conv_s2k4_patch_dgrad16_supported(int B, int Ho, int hin, int cin, int cout, int k, int s_) {
+    int t, g;
+    return dg_plan(B, Ho, hin, cin, cout, k, s_, false, 0, 0, 0, t, g);
+}
+bool conv_s2k4_patch_dgrad16_stem_supported(int B, int Ho, int hin, int cin, int cout, int k, int s_, int stem_hin, int stem_s, long long stem_part_cap) {
+    int t, g;
+    return dg_plan(B, Ho, hin, cin, cout, k, s_, true, stem_hin, stem_s, stem_part_cap, t, g);
+}
+
+// dout: bf16 NHWC [B][Ho][Ho][128]; wd[q]: bf16 [128 ci][4 taps * 128 co] of output-parity class q = py * 2 + px (k_prep mode 3); gate: the
+// stored activation of the layer below, bf16 NHWC [B][2 (Ho + 1)][2 (Ho + 1)][128]; out: d of that activation (same layout), or -- when
+// stem_part != nullptr -- nothing: the stem's weight / bias gradient is accumulated into stem_dw [128][16] / stem_db [128] instead.
+int conv_s2k4_patch_dgrad16(const void* dout, const void* const* wd, const void* gate, void* out, int B, int Ho, int hin, int cin, int cout, int k,
+                            int s_, const float* stem_xp, int stem_hin, int stem_s, float* stem_part, long long stem_part_cap, float* stem_dw,
+                            float* stem_db, hipStream_t s, const void* gate_bits) {
     const bool stem = stem_part != nullptr;
-    const int n_cu = spair_num_cus();
-    const int grid = std::min(tiles, n_cu);      // persistent: one 160-KB workgroup per CU walks the tiles
-    // one [128][17] partial per workgroup; the caller retries without the stem fusion when this is refused
-    if (stem && (!stem_xp || !stem_dw || (long long)grid * DG_STEM_FLOATS > stem_part_cap || (stem_hin & 1) || (stem_s & 1))) return SPAIR_ERR_UNSUPPORTED;
+    int tpi = 0, grid = 0;
+    if (!dg_plan(B, Ho, hin, cin, cout, k, s_, stem, stem_hin, stem_s, stem_part_cap, tpi, grid) || (stem && (!stem_xp || !stem_dw)))
+        return SPAIR_ERR_UNSUPPORTED;
+    const int Hc = Ho + 1;
+    const long long M = (long long)B * Hc * Hc;
     ConvDgradArgs a;
     a.dout = reinterpret_cast<const u16*>(dout);
     for (int q = 0; q < 4; ++q) a.Bz[q] = reinterpret_cast<const u16*>(wd[q]);

@@ -7,9 +7,9 @@
 #include <stdio.h>
 #include <algorithm>
 #include <mutex>
-#include <functional>
 #include <vector>
 
+#include "backbone.h"
 #include "cells.h"
 #include "gemm.h"
 #include "misc.h"
@@ -399,8 +399,17 @@ struct Ctx {
     int use_dec_fused;     // the decoder forward as one activation-stationary kernel (bf16; SpairStep.flags bit 4 turns it off)
     RenderGeom rg;         // the renderer's objects: the rows' nbox, presence and depth
     RenderPlan rp;         // the renderer's kernels and sprite / d-logit formats (render.h)
-    float* tn_scratch = nullptr;   // split-K scratch override while work is being issued on the helper stream
-    bool keep_dact0 = false;       // spair_backward_x: d act0 goes to HBM (the stem's data gradient reads it), no stem fusion into conv_1
+    bool use_side;         // the helper stream (SpairStep.flags bit 2 turns it off)
+    // the backbone's kernels, per layer 1 .. PL.n_conv - 1 (the bf16 step's patch-resident ones: flags bit 5 turns them off)
+    int pw0;               // first layer of the fused trailing 1x1 stack (PL.n_conv: none)
+    ConvKernel conv_fwd[SP_MAX_CONV + 1], conv_dgrad[SP_MAX_CONV + 1];
+    const unsigned char* dgrad_bits[SP_MAX_CONV + 1];      // a patch dgrad's gate: the sign bits the layer below left (null: its activation)
+    StemWgrad stem_wgrad;
+    // the bf16 step's decoder backward
+    bool dec_dgrad_fused;  // the three data gradients in one launch (dec_fused_bwd.hip; flags bit 6 turns it off)
+    bool dec_wgrad_grouped;    // the two small weight gradients in one grouped launch
+    bool dec_wgrad_late;   // the weight gradients issued behind the chain backward's launch (helper stream and fused chain)
+    float* tn_part;        // split-K scratch of c.s: w.tn_part, w.tn_part2 on the helper stream (OnHelper)
     std::vector<int> dstart;
 };
 
@@ -454,6 +463,13 @@ static int stream_link(hipStream_t from, hipStream_t to, hipEvent_t e) {
     if (hipStreamWaitEvent(to, e, 0) != hipSuccess) return SPAIR_ERR_LAUNCH;
     return SPAIR_OK;
 }
+// While in scope, work is issued on the helper stream (side; null: no helper stream, nothing changes) together with its own split-K scratch
+// tn_part2 -- a split-K GEMM there must not share tn_part with the caller's stream.  Both are restored on every exit path.
+struct OnHelper {
+    Ctx& c; hipStream_t s0; float* part0;
+    OnHelper(Ctx& ctx, const SideStream* side) : c(ctx), s0(ctx.s), part0(ctx.tn_part) { if (side) { c.s = side->s; c.tn_part = c.w.tn_part2; } }
+    ~OnHelper() { c.s = s0; c.tn_part = part0; }
+};
 
 static void fill_diag(Ctx& c) {
     const int G = c.d.G;
@@ -471,55 +487,27 @@ static void fill_diag(Ctx& c) {
     c.dstart[c.T] = n;
 }
 
-// Which kernels the step runs (host arithmetic on c.d, c.L, c.PL and c.w only): make_ctx and the spair_step_plan diagnostic
-static void plan_step(Ctx& c, int flags) {
-    const SpairDims& d = c.d;
-    c.use_chain = chain_fwd_supported(d) && !(flags & 1) && !d.obj_conv;
-    c.rg = {c.w.cb.nbox, c.w.cb.rec + (c.L.REC - 1), c.w.cb.rec + (c.L.REC - 2), c.L.ld_rec, d.B, c.L.HW, d.I, d.P, d.align_corners};
-    c.rp = render_plan(d, c.rg, c.w.ld_s, c.w.S, c.w.rrec, c.w.dLog);
-    c.use_dec_fused = c.rp.s16 /* it writes fp16 sprites */ && !(flags & 16) && c.PL.lin[LIN_DEC0].out == SP_DEC_H1 && c.PL.lin[LIN_DEC1].out == SP_DEC_H2 &&
-                      dec_fused_supported(d.A, d.P * d.P * (d.C + 1), c.L.ld_rec, c.L.N, c.w.ld_s);
-}
-
-static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
-                    const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace, void* stream) {
-    if (!d || !st || !params || !x || !workspace) return SPAIR_ERR_SHAPE;
-    TRY(validate(*d));
-    c.d = *d; c.st = *st;
-    c.L = make_cell_layout(*d);
-    c.PL = make_param_layout(*d);
-    c.w = carve(*d, workspace);
-    c.params = params; c.x = x; c.s = (hipStream_t)stream;
-    CellHyper& H = c.H;
-    H.wheel = st->wheel; H.kl_scale = st->kl_scale * d->vae_beta; H.img = (float)d->I; H.anchor = d->anchor;
-    H.cell_over_img = (float)((double)d->cell_px / (double)d->I);
-    H.max_yx = d->max_yx; H.min_yx = d->min_yx; H.max_hw = d->max_hw; H.min_hw = d->min_hw;
-    H.range_yx = d->max_yx - d->min_yx; H.range_hw = d->max_hw - d->min_hw;
-    for (int i = 0; i < 6; ++i) { H.prior_mean[i] = d->prior_mean[i]; H.prior_std[i] = d->prior_std[i]; }
-    H.count_prior_prob = st->count_prior_prob;
-    c.w.cb.edge = params + c.PL.edge;
-    c.w.cb.eps_box = eps_box; c.w.cb.eps_attr = eps_attr; c.w.cb.eps_depth = eps_depth; c.w.cb.u_pres = u_pres;
-    fill_diag(c);
-    plan_step(c, st->flags);
-    return SPAIR_OK;
-}
-
 // ---- GEMM helpers ---------------------------------------------------------------------------------
 static int nt(Ctx& c, const float* A, int lda, const void* B, int ldb, float* C, int ldc, int M, int N, int K, const float* bias,
-              const float* mask, int ldmask, int relu) {
+              const float* mask, int ldmask, int relu, const ConvDesc* conv = nullptr, const RowMap* cmap = nullptr) {
     GemmNT g;
     memset(&g, 0, sizeof(g));
     g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
     g.bias = bias; g.mask = mask; g.ldmask = ldmask; g.relu = relu;
-    return spair_gemm_nt_impl(g, false, c.d.dtype, c.s);
+    if (conv) g.conv = *conv;
+    if (cmap) { g.cmap = *cmap; g.use_cmap = 1; }
+    return spair_gemm_nt_impl(g, conv != nullptr, c.d.dtype, c.s);
 }
-static int tn(Ctx& c, const float* A, int lda, int M, const float* B, int ldb, int N, float* C, int ldc, int R, float* colsum = nullptr) {
+static int tn(Ctx& c, const float* A, int lda, int M, const float* B, int ldb, int N, float* C, int ldc, int R, float* colsum = nullptr,
+              const ConvDesc* conv = nullptr, int cw_cin = 0, int cw_taps = 0) {
     GemmTN g;
     memset(&g, 0, sizeof(g));
     g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
     g.M = round_up(M, 4); g.N = round_up(N, 4); g.Mstore = M; g.Nstore = N; g.R = R; g.colsum_out = colsum;
+    g.cw_cin = cw_cin; g.cw_taps = cw_taps;
+    if (conv) g.conv = *conv;
     // (split-K partial tiles do not pay here: N-contiguous atomics on 1-3 tiles are cheaper than the extra pass)
-    return spair_gemm_tn_impl(g, false, c.d.dtype, c.s);
+    return spair_gemm_tn_impl(g, conv != nullptr, c.d.dtype, c.s);
 }
 // bf16-stored operand GEMMs (gemm16.hip)
 // strided k x k convs of the bf16 step keep their forward weights in tap-parity K order (gemm.h, GemmNT::ktab)
@@ -554,7 +542,7 @@ static int tn16(Ctx& c, const void* A, int lda, int M, const void* B, int ldb, i
     g.A = reinterpret_cast<const float*>(A); g.lda = lda; g.B = reinterpret_cast<const float*>(B); g.ldb = ldb; g.C = C; g.ldc = ldc;
     g.M = round_up(M, 8); g.N = round_up(N, b_bf16 ? 8 : 4); g.Mstore = M; g.Nstore = N; g.R = R; g.colsum_out = colsum;
     g.cw_cin = cw_cin; g.cw_taps = cw_taps;
-    g.part = c.tn_scratch ? c.tn_scratch : c.w.tn_part; g.part_cap = SPAIR_TN_PART_FLOATS;
+    g.part = c.tn_part; g.part_cap = SPAIR_TN_PART_FLOATS;
     if (conv) g.conv = *conv;
     return spair_gemm_tn16_impl(g, conv != nullptr, b_bf16, c.s);
 }
@@ -683,20 +671,115 @@ static ConvDesc fwd_desc(const ConvSpec& cs) {
     return cd;
 }
 
-// First layer of the trailing run of 1x1 convolutions that pointwise.hip can fuse (128 channels in, 128 out except the last,
-// at most 4 layers), or n_conv if there is none.
-static int pw_stack_first(const Ctx& c) {
-    const int n = c.PL.n_conv;
-    if (c.d.dtype != SPAIR_BF16) return n;
-    int i0 = n;
-    for (int i = n - 1; i >= 1; --i) {
+// The data gradient of strided layer cs into the output-parity class (py, px) of its input: a stride-1 implicit GEMM over d out (gather dd),
+// stored through the row map rm.  Returns the class's pixels per image (0: the class is empty).
+static int dgrad_class(const ConvSpec& cs, int py, int px, ConvDesc& dd, RowMap& rm) {
+    const int T = cs.k / cs.s;
+    const int Hc = (cs.hin - py + cs.s - 1) / cs.s, Wc = (cs.hin - px + cs.s - 1) / cs.s;
+    dd.Hin = cs.hout; dd.Win = cs.hout; dd.Cin = cs.cout; dd.Hout = Hc; dd.Wout = Wc; dd.kh = T; dd.kw = T;
+    dd.sy = 1; dd.sx = 1; dd.dky = -1; dd.dkx = -1; dd.oy = 0; dd.ox = 0;
+    rm.Hout = Hc; rm.Wout = Wc; rm.Hc = cs.hin; rm.Wc = cs.hin; rm.osy = cs.s; rm.osx = cs.s; rm.ooy = py; rm.oox = px;
+    return Hc > 0 && Wc > 0 ? Hc * Wc : 0;
+}
+// All output-parity classes of layer i's data gradient in one nt16 launch (blockIdx.z = class; they have the same size): d out (A) is the
+// caller's.  Layer 1 also carries the stem's input and scratch -- the launch keeps stem_part where the plan fuses the stem's weight gradient.
+static GemmNT dgrad_classes16(const Ctx& c, int i) {
+    const ConvSpec &cs = c.PL.conv[i], &c0 = c.PL.conv[0];
+    const int T = cs.k / cs.s;
+    GemmNT g;
+    memset(&g, 0, sizeof(g));
+    g.M = c.d.B * dgrad_class(cs, 0, 0, g.conv, g.cmap); g.use_cmap = 1; g.N = cs.cin; g.K = T * T * cs.cout;
+    g.ldb = g.K; g.C = c.w.dact[i - 1]; g.ldc = cs.cin; g.c_bf16 = 1; g.mask = c.w.act[i - 1]; g.ldmask = cs.cin; g.mask_bf16 = 1;
+    g.nz = cs.s * cs.s;
+    for (int q = 0; q < g.nz; ++q) g.Bz[q] = c.w.conv_wd[i][q];
+    g.B = g.Bz[0];
+    if (i == 1) { g.stem_xp = c.w.xpad; g.stem_hin = c0.hin; g.stem_s = c0.s; g.stem_part = c.w.tn_part; g.stem_part_cap = SPAIR_TN_PART_FLOATS; }
+    return g;
+}
+
+// The decoder's two small weight gradients as one grouped launch (decoder_small_wgrad_grouped): whole layers of at most 128 inputs, in tiles
+// of 128 output rows, operands addressed with 32-bit offsets
+static bool decoder_small_wgrad_grouped_supported(const Ctx& c) {
+    const LinSpec &l1 = c.PL.lin[LIN_DEC1], &l0 = c.PL.lin[LIN_DEC0];
+    return l1.in <= 128 && l0.in <= 128 && !(l1.out & 7) && !(l0.out & 7) && ceil_div(l1.out, 128) + ceil_div(l0.out, 128) <= SPAIR_TN_MAX_TILES &&
+           std::min(round_up(l1.in, 8), SP_DEC_H1) >= l1.in && std::min(round_up(l0.in, 8), c.L.ld_rec) >= l0.in &&
+           (long long)c.L.N * std::max(SP_DEC_H2, c.L.ld_rec) < (1ll << 31);
+}
+
+// ---- step plan -----------------------------------------------------------------------------------------
+// Which kernels the step runs (host arithmetic on c.d, c.L, c.PL and c.w only): make_ctx and the spair_step_plan diagnostics.  input_grad
+// (spair_backward_x): the image gradient reads d act0 from HBM, so the stem's weight gradient is not fused into conv_1's data gradient.
+static void plan_step(Ctx& c, int flags, bool input_grad) {
+    const SpairDims& d = c.d;
+    const bool b16 = d.dtype == SPAIR_BF16;
+    c.use_chain = chain_fwd_supported(d) && !(flags & 1) && !d.obj_conv;
+    c.rg = {c.w.cb.nbox, c.w.cb.rec + (c.L.REC - 1), c.w.cb.rec + (c.L.REC - 2), c.L.ld_rec, d.B, c.L.HW, d.I, d.P, d.align_corners};
+    c.rp = render_plan(d, c.rg, c.w.ld_s, c.w.S, c.w.rrec, c.w.dLog);
+    c.use_dec_fused = c.rp.s16 /* it writes fp16 sprites */ && !(flags & 16) && c.PL.lin[LIN_DEC0].out == SP_DEC_H1 && c.PL.lin[LIN_DEC1].out == SP_DEC_H2 &&
+                      dec_fused_supported(d.A, d.P * d.P * (d.C + 1), c.L.ld_rec, c.L.N, c.w.ld_s);
+    c.use_side = !(flags & 4);
+    // backbone
+    const ConvSpec& c0 = c.PL.conv[0];
+    const bool grey4 = c0.cin == 1 && c0.k == 4 && c0.cout == 128;
+    const bool fuse_stem = b16 && grey4 && !(flags & 8) && !input_grad;
+    const bool patch = b16 && !(flags & 32);
+    c.stem_wgrad = b16 && grey4 ? STEM_WGRAD16 : STEM_GENERIC;
+    const int n = c.PL.n_conv;      // the trailing run of 1x1 layers pointwise.hip fuses: 128 channels in, 128 out except the last, 2 to 4 layers
+    c.pw0 = n;
+    for (int i = n - 1; b16 && i >= 1; --i) {
         const ConvSpec& cs = c.PL.conv[i];
-        const bool last = (i == n - 1);
-        if (cs.k != 1 || cs.s != 1 || cs.cin != 128 || (last ? cs.cout > 128 : cs.cout != 128) || n - i > 4) break;
-        if (c.PL.conv[i - 1].cout != 128) break;
-        i0 = i;
+        if (cs.k != 1 || cs.s != 1 || cs.cin != 128 || (i == n - 1 ? cs.cout > 128 : cs.cout != 128) || n - i > 4 || c.PL.conv[i - 1].cout != 128) break;
+        c.pw0 = i;
     }
-    return (n - i0 >= 2) ? i0 : n;
+    if (n - c.pw0 < 2) c.pw0 = n;
+    const unsigned char* bits = c.w.act0_bits;     // what the forward of the layer below leaves: the stem kernel's sign bits (misc_conv0_writes_mask)
+    for (int i = 1; i < n; ++i) {
+        const ConvSpec& cs = c.PL.conv[i];
+        c.dgrad_bits[i] = nullptr;
+        if (i >= c.pw0) { c.conv_fwd[i] = c.conv_dgrad[i] = CONV_PW_STACK; continue; }
+        c.conv_fwd[i] = patch && conv_s2k4_patch_fwd16_supported(d.B, cs.hin, cs.hout, cs.cin, cs.cout, cs.k, cs.s) ? CONV_PATCH : CONV_GEMM;
+        if (cs.k == 1) c.conv_dgrad[i] = CONV_GEMM;
+        else if (patch && conv_s2k4_patch_dgrad16_supported(d.B, cs.hout, cs.hin, cs.cin, cs.cout, cs.k, cs.s)) {
+            c.conv_dgrad[i] = CONV_PATCH;
+            c.dgrad_bits[i] = bits;
+            if (i == 1 && fuse_stem &&
+                conv_s2k4_patch_dgrad16_stem_supported(d.B, cs.hout, cs.hin, cs.cin, cs.cout, cs.k, cs.s, c0.hin, c0.s, SPAIR_TN_PART_FLOATS))
+                c.stem_wgrad = STEM_PATCH;
+        } else if (b16 && cs.hin % cs.s == 0 && cs.s * cs.s <= 4) {
+            c.conv_dgrad[i] = CONV_GEMM;
+            if (i == 1 && fuse_stem && spair_nt16_stem_fusable(dgrad_classes16(c, 1), SPAIR_TN_PART_FLOATS)) c.stem_wgrad = STEM_GEMM;
+        } else c.conv_dgrad[i] = CONV_PER_CLASS;
+        bits = c.conv_fwd[i] == CONV_PATCH ? c.w.act_bits[i] : nullptr;
+    }
+    // the bf16 step's MLP decoder backward
+    const bool dec16 = b16 && !c.PL.oc_n;
+    const int per = d.P * d.P * (d.C + 1);
+    c.dec_dgrad_fused = dec16 && !(flags & 64) && dec_fused_bwd_supported(c.PL.lin[LIN_DEC0].in, per, c.L.N, c.w.ld_s, round_up(per, 8), c.L.ld_rec);
+    c.dec_wgrad_grouped = dec16 && decoder_small_wgrad_grouped_supported(c);
+    c.dec_wgrad_late = dec16 && c.use_side && c.use_chain;
+}
+
+static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
+                    const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace, void* stream, bool input_grad = false) {
+    if (!d || !st || !params || !x || !workspace) return SPAIR_ERR_SHAPE;
+    TRY(validate(*d));
+    c.d = *d; c.st = *st;
+    c.L = make_cell_layout(*d);
+    c.PL = make_param_layout(*d);
+    c.w = carve(*d, workspace);
+    c.params = params; c.x = x; c.s = (hipStream_t)stream; c.tn_part = c.w.tn_part;
+    CellHyper& H = c.H;
+    H.wheel = st->wheel; H.kl_scale = st->kl_scale * d->vae_beta; H.img = (float)d->I; H.anchor = d->anchor;
+    H.cell_over_img = (float)((double)d->cell_px / (double)d->I);
+    H.max_yx = d->max_yx; H.min_yx = d->min_yx; H.max_hw = d->max_hw; H.min_hw = d->min_hw;
+    H.range_yx = d->max_yx - d->min_yx; H.range_hw = d->max_hw - d->min_hw;
+    for (int i = 0; i < 6; ++i) { H.prior_mean[i] = d->prior_mean[i]; H.prior_std[i] = d->prior_std[i]; }
+    H.count_prior_prob = st->count_prior_prob;
+    c.w.cb.edge = params + c.PL.edge;
+    c.w.cb.eps_box = eps_box; c.w.cb.eps_attr = eps_attr; c.w.cb.eps_depth = eps_depth; c.w.cb.u_pres = u_pres;
+    fill_diag(c);
+    plan_step(c, st->flags, input_grad);
+    return SPAIR_OK;
 }
 
 // input padding + the stem conv: they read the fp32 parameters directly, so they do not wait for the weight preparation
@@ -713,12 +796,12 @@ static int backbone_stem_fwd(Ctx& c) {
 static int backbone_fwd(Ctx& c) {
     const SpairDims& d = c.d;
     const int b16 = d.dtype == SPAIR_BF16;
-    const int pw0 = pw_stack_first(c);
+    const int pw0 = c.pw0;
     for (int i = 1; i < c.PL.n_conv; ++i) {
         const ConvSpec& cs = c.PL.conv[i];
         const bool last = (i == c.PL.n_conv - 1);
         const int M = d.B * cs.hout * cs.hout, K = cs.k * cs.k * cs.cin;
-        if (i == pw0) {   // the trailing 1x1 layers run as one fused per-pixel MLP
+        if (c.conv_fwd[i] == CONV_PW_STACK) {   // the trailing 1x1 layers (from pw0 on) run as one fused per-pixel MLP
             const void* W[4]; const float* bias[4]; void* Y[4]; int ldw[4], cout[4];
             const int Lp = c.PL.n_conv - pw0;
             for (int l = 0; l < Lp; ++l) {
@@ -731,27 +814,20 @@ static int backbone_fwd(Ctx& c) {
         float* out = last ? c.w.feat : c.w.act[i];
         const int ldc = last ? c.w.ld_feat : cs.cout;
         const ConvDesc cd = fwd_desc(cs);
-        if (b16 && !last && cs.k > 1 && conv_kperm(c, cs) && !(c.st.flags & 32)) {
-            // 128 -> 128 channel 4x4 / stride-2 layers: the patch-resident kernel (conv_s2.hip), 2.3x fewer operand bytes from L2
+        if (c.conv_fwd[i] == CONV_PATCH) {
+            // 128 -> 128 channel 4x4 / stride-2 layers: the patch-resident kernel (conv_s2.hip), 2.3x fewer operand bytes from L2 (+ its sign bits)
             ProfScope ps(i == 1 ? PS_CONV1_FWD : -1, c.s);
-            const int rc = conv_s2k4_patch_fwd16(c.w.act[i - 1], c.w.conv_wf[i], c.params + cs.b, out, d.B, cs.hin, cs.hout, cs.cin, cs.cout, cs.k, cs.s, c.s,
-                                                 c.w.act_bits[i]);      // (also with train = 0: the backward picks its gate from the geometry alone)
-            if (rc == SPAIR_OK) continue;
-            if (rc != SPAIR_ERR_UNSUPPORTED) return rc;
-        }
-        if (b16) {   // activations stored as bf16; the feature map handed to the per-cell chain stays fp32
+            TRY(conv_s2k4_patch_fwd16(c.w.act[i - 1], c.w.conv_wf[i], c.params + cs.b, out, d.B, cs.hin, cs.hout, cs.cin, cs.cout, cs.k, cs.s, c.s,
+                                      c.w.act_bits[i]));
+        } else if (b16) {   // activations stored as bf16; the feature map handed to the per-cell chain stays fp32
             ProfScope ps(i == 1 ? PS_CONV1_FWD : -1, c.s);
             TRY(nt16(c, c.w.act[i - 1], cs.cin, c.w.conv_wf[i], round_up(K, 8), out, ldc, last ? 0 : 1, M, cs.cout, round_up(K, 8),
                      c.params + cs.b, nullptr, 0, last ? 0 : 1, cs.k == 1 ? nullptr : &cd, nullptr, cs.k == 1 ? nullptr : &cs));
         } else if (cs.k == 1) {
             TRY(nt(c, c.w.act[i - 1], cs.cin, c.w.conv_wf[i], round_up(K, 8), out, ldc, M, cs.cout, round_up(K, 8), c.params + cs.b, nullptr, 0, last ? 0 : 1));
         } else {
-            GemmNT g;
-            memset(&g, 0, sizeof(g));
-            g.A = c.w.act[i - 1]; g.B = c.w.conv_wf[i]; g.ldb = round_up(K, 8); g.C = out; g.ldc = ldc; g.M = M; g.N = cs.cout; g.K = K;
-            g.bias = c.params + cs.b; g.relu = last ? 0 : 1; g.conv = cd;
             ProfScope ps(i == 1 ? PS_CONV1_FWD : -1, c.s);
-            TRY(spair_gemm_nt_impl(g, true, d.dtype, c.s));
+            TRY(nt(c, c.w.act[i - 1], 0, c.w.conv_wf[i], round_up(K, 8), out, ldc, M, cs.cout, K, c.params + cs.b, nullptr, 0, last ? 0 : 1, &cd));
         }
     }
     return SPAIR_OK;
@@ -759,11 +835,10 @@ static int backbone_fwd(Ctx& c) {
 
 static int backbone_bwd16(Ctx& c, float* grads) {
     const SpairDims& d = c.d;
-    const int last = c.PL.n_conv - 1;
-    bool stem_fused = false;
+    const int last = c.PL.n_conv - 1, pw0 = c.pw0;
+    const ConvSpec& c0 = c.PL.conv[0];
     const int N = d.B * d.G * d.G;
     if (!c.use_chain) TRY(spair_to_bf16(c.w.dfeat, c.w.ld_feat, c.w.dfeat16, c.w.ld_feat, N, c.w.ld_feat, c.s));   // the fused chain writes bf16 itself
-    const int pw0 = pw_stack_first(c);
     if (pw0 <= last) {   // data gradients of the trailing 1x1 layers: one fused kernel, top layer first
         const void* Wd[4]; const void* gate[4]; void* dX[4]; int ldw[4], cout[4];
         const int Lp = last - pw0 + 1;
@@ -773,8 +848,7 @@ static int backbone_bwd16(Ctx& c, float* grads) {
             Wd[l] = c.w.conv_wd[i][0]; ldw[l] = round_up(q.cout, 8); cout[l] = q.cout; gate[l] = c.w.act[i - 1]; dX[l] = c.w.dact[i - 1];
         }
         TRY(spair_pw_stack_bwd16(c.w.dfeat16, c.w.ld_feat, c.PL.conv[last].cout, Wd, ldw, cout, gate, dX, N, Lp, c.s));
-    }
-    if (pw0 <= last) {   // ... and their weight / bias gradients as ONE grouped split-K GEMM + one reduce pass
+        // ... and their weight / bias gradients as ONE grouped split-K GEMM + one reduce pass
         GemmTN g;
         memset(&g, 0, sizeof(g));
         g.ngroup = last - pw0 + 1;
@@ -789,100 +863,62 @@ static int backbone_bwd16(Ctx& c, float* grads) {
             t.M = round_up(cs.cout, 8); t.N = cs.cin; t.Mstore = cs.cout; t.Nstore = cs.cin;
         }
         g.R = N;
-        g.part = c.tn_scratch ? c.tn_scratch : c.w.tn_part; g.part_cap = SPAIR_TN_PART_FLOATS;
+        g.part = c.tn_part; g.part_cap = SPAIR_TN_PART_FLOATS;
         TRY(spair_gemm_tn16_impl(g, false, true, c.s));
     }
-    for (int i = last; i >= 1; --i) {
+    for (int i = pw0 - 1; i >= 1; --i) {      // (the layers below the 1x1 stack)
         const ConvSpec& cs = c.PL.conv[i];
         const int M = d.B * cs.hout * cs.hout;
         const void* dout = (i == last) ? c.w.dfeat16 : (const void*)c.w.dact[i];
         const int ldd = (i == last) ? c.w.ld_feat : cs.cout;
         const void* in = c.w.act[i - 1];
-        const ConvDesc cd = fwd_desc(cs);
         if (cs.k == 1) {
-            if (i >= pw0) continue;
             TRY(tn16(c, dout, ldd, cs.cout, in, cs.cin, cs.cin, true, grads + cs.w, cs.cin, M, grads + cs.b));
             const int Kd = round_up(cs.cout, 8);
-            if (i < pw0) TRY(nt16(c, dout, ldd, c.w.conv_wd[i][0], Kd, c.w.dact[i - 1], cs.cin, 1, M, cs.cin, Kd, nullptr, in, cs.cin, 0));
-        } else {
-            const int K = cs.k * cs.k * cs.cin;
-            TRY(tn16(c, dout, ldd, cs.cout, in, 0, K, true, grads + cs.w, K, M, grads + cs.b, &cd, cs.cin, cs.k * cs.k));
-            const int T = cs.k / cs.s;
-            if (cs.k == 4 && cs.s == 2 && cs.cin == 128 && cs.cout == 128 && cs.hin == 2 * (cs.hout + 1) && !(c.st.flags & 32)) {
-                // patch-resident data gradient (conv_s2_dgrad.hip): the d-out neighbourhood of a tile is staged once for all 4 parity classes x 4 taps
-                const ConvSpec& c0 = c.PL.conv[0];
-                const bool want_stem = i == 1 && c0.cin == 1 && c0.k == 4 && c0.cout == 128 && c0.hout == cs.hin && !(c.st.flags & 8) &&
-                                       !c.keep_dact0;
-                const void* wd4[4] = {c.w.conv_wd[i][0], c.w.conv_wd[i][1], c.w.conv_wd[i][2], c.w.conv_wd[i][3]};
-                // conv_1's gate as the stem kernel's sign bits (20 MB instead of the 321-MB activation) whenever that kernel wrote them
-                const void* gbits = nullptr;
-                if (i == 1) { if (c0.hout == cs.hin) gbits = c.w.act0_bits; }
-                else {          // the layer below ran on the patch-resident forward kernel (same test as backbone_fwd): it left its mask
-                    const ConvSpec& lo = c.PL.conv[i - 1];
-                    if (lo.k > 1 && conv_kperm(c, lo) && conv_s2k4_patch_fwd16_fits(d.B, lo.hin, lo.hout, lo.cin, lo.cout, lo.k, lo.s)) gbits = c.w.act_bits[i - 1];
-                }
-                int rc = conv_s2k4_patch_dgrad16(dout, wd4, in, c.w.dact[i - 1], d.B, cs.hout, cs.hin, cs.cin, cs.cout, cs.k, cs.s,
-                                                 want_stem ? c.w.xpad : nullptr, c0.hin, c0.s, want_stem ? c.w.tn_part : nullptr,
-                                                 SPAIR_TN_PART_FLOATS, grads + c0.w, grads + c0.b, c.s, gbits);
-                if (rc == SPAIR_OK) { if (want_stem) stem_fused = true; continue; }
-                if (rc == SPAIR_ERR_UNSUPPORTED && want_stem) {      // the stem fusion alone was refused: same kernel, d act0 to HBM, stem wgrad below
-                    rc = conv_s2k4_patch_dgrad16(dout, wd4, in, c.w.dact[i - 1], d.B, cs.hout, cs.hin, cs.cin, cs.cout, cs.k, cs.s, nullptr, 0, 0,
-                                                 nullptr, 0, nullptr, nullptr, c.s, gbits);
-                    if (rc == SPAIR_OK) continue;
-                }
-                if (rc != SPAIR_ERR_UNSUPPORTED) return rc;
+            TRY(nt16(c, dout, ldd, c.w.conv_wd[i][0], Kd, c.w.dact[i - 1], cs.cin, 1, M, cs.cin, Kd, nullptr, in, cs.cin, 0));
+            continue;
+        }
+        const int K = cs.k * cs.k * cs.cin;
+        const ConvDesc cd = fwd_desc(cs);
+        TRY(tn16(c, dout, ldd, cs.cout, in, 0, K, true, grads + cs.w, K, M, grads + cs.b, &cd, cs.cin, cs.k * cs.k));
+        const int T = cs.k / cs.s;
+        if (c.conv_dgrad[i] == CONV_PATCH) {
+            // patch-resident data gradient (conv_s2_dgrad.hip): the d-out neighbourhood of a tile is staged once for all 4 parity classes x 4 taps;
+            // conv_1's gate as the stem kernel's sign bits where it wrote them (20 MB instead of the 321-MB activation)
+            const bool stem = i == 1 && c.stem_wgrad == STEM_PATCH;
+            const void* wd4[4] = {c.w.conv_wd[i][0], c.w.conv_wd[i][1], c.w.conv_wd[i][2], c.w.conv_wd[i][3]};
+            TRY(conv_s2k4_patch_dgrad16(dout, wd4, in, c.w.dact[i - 1], d.B, cs.hout, cs.hin, cs.cin, cs.cout, cs.k, cs.s, stem ? c.w.xpad : nullptr,
+                                        c0.hin, c0.s, stem ? c.w.tn_part : nullptr, SPAIR_TN_PART_FLOATS, grads + c0.w, grads + c0.b, c.s,
+                                        c.dgrad_bits[i]));
+        } else if (c.conv_dgrad[i] == CONV_GEMM) {
+            // all output-parity classes in one launch, blockIdx.z = class (4 launches of 1.1 rounds of resident blocks each ran as 2 rounds:
+            // conv2's data-gradient took 0.37 ms for 34 GFLOP); conv_1 may take the stem's weight gradient from the tile in LDS
+            GemmNT g = dgrad_classes16(c, i);
+            g.A = reinterpret_cast<const float*>(dout);
+            if (i == 1) {
+                g.stem_dw = grads + c0.w; g.stem_db = grads + c0.b;
+                if (c.stem_wgrad != STEM_GEMM) g.stem_part = nullptr;
             }
-            if (cs.hin % cs.s == 0 && cs.s * cs.s <= 4) {
-                // all output-parity classes have the same size: one launch, blockIdx.z = class (4 launches of 1.1 rounds of
-                // resident blocks each ran as 2 rounds: conv2's data-gradient took 0.37 ms for 34 GFLOP)
-                const int Hc = cs.hin / cs.s;
-                GemmNT g;
-                memset(&g, 0, sizeof(g));
-                g.A = reinterpret_cast<const float*>(dout); g.ldb = T * T * cs.cout; g.C = c.w.dact[i - 1]; g.ldc = cs.cin; g.c_bf16 = 1;
-                g.M = d.B * Hc * Hc; g.N = cs.cin; g.K = T * T * cs.cout;
-                g.mask = reinterpret_cast<const float*>(in); g.ldmask = cs.cin; g.mask_bf16 = 1;
-                g.conv.Hin = cs.hout; g.conv.Win = cs.hout; g.conv.Cin = cs.cout; g.conv.Hout = Hc; g.conv.Wout = Hc; g.conv.kh = T; g.conv.kw = T;
-                g.conv.sy = 1; g.conv.sx = 1; g.conv.dky = -1; g.conv.dkx = -1; g.conv.oy = 0; g.conv.ox = 0;
-                g.use_cmap = 1;
-                g.cmap.Hout = Hc; g.cmap.Wout = Hc; g.cmap.Hc = cs.hin; g.cmap.Wc = cs.hin; g.cmap.osy = cs.s; g.cmap.osx = cs.s;
-                g.nz = cs.s * cs.s;
-                for (int q = 0; q < g.nz; ++q) g.Bz[q] = c.w.conv_wd[i][q];
-                g.B = g.Bz[0];
-                if (i == 1) {     // conv_1: take the stem's weight gradient from the tile in LDS; d act0 never reaches HBM
-                    const ConvSpec& c0 = c.PL.conv[0];
-                    g.stem_xp = c.w.xpad; g.stem_hin = c0.hin; g.stem_s = c0.s; g.stem_dw = grads + c0.w; g.stem_db = grads + c0.b;
-                    g.stem_part = c.w.tn_part; g.stem_part_cap = SPAIR_TN_PART_FLOATS;
-                    stem_fused = c0.cin == 1 && c0.k == 4 && c0.cout == 128 && c0.hout == cs.hin && !(c.st.flags & 8) && !c.keep_dact0 &&
-                                 spair_nt16_stem_fusable(g, g.stem_part_cap);
-                    if (!stem_fused) g.stem_part = nullptr;
-                }
-                TRY(spair_gemm_nt16_impl(g, true, c.s));
-            } else
+            TRY(spair_gemm_nt16_impl(g, true, c.s));
+        } else {
             for (int py = 0; py < cs.s; ++py)
                 for (int px = 0; px < cs.s; ++px) {
-                    const int Hc = (cs.hin - py + cs.s - 1) / cs.s, Wc = (cs.hin - px + cs.s - 1) / cs.s;
-                    if (Hc <= 0 || Wc <= 0) continue;
-                    ConvDesc dd;
-                    dd.Hin = cs.hout; dd.Win = cs.hout; dd.Cin = cs.cout; dd.Hout = Hc; dd.Wout = Wc; dd.kh = T; dd.kw = T;
-                    dd.sy = 1; dd.sx = 1; dd.dky = -1; dd.dkx = -1; dd.oy = 0; dd.ox = 0;
-                    RowMap rm;
-                    rm.Hout = Hc; rm.Wout = Wc; rm.Hc = cs.hin; rm.Wc = cs.hin; rm.osy = cs.s; rm.osx = cs.s; rm.ooy = py; rm.oox = px;
-                    TRY(nt16(c, dout, 0, c.w.conv_wd[i][py * cs.s + px], T * T * cs.cout, c.w.dact[i - 1], cs.cin, 1, d.B * Hc * Wc, cs.cin,
-                             T * T * cs.cout, nullptr, in, cs.cin, 0, &dd, &rm));
+                    ConvDesc dd; RowMap rm;
+                    const int rows = dgrad_class(cs, py, px, dd, rm);
+                    if (rows) TRY(nt16(c, dout, 0, c.w.conv_wd[i][py * cs.s + px], T * T * cs.cout, c.w.dact[i - 1], cs.cin, 1, d.B * rows, cs.cin,
+                                       T * T * cs.cout, nullptr, in, cs.cin, 0, &dd, &rm));
                 }
         }
     }
-    if (!stem_fused) {   // first layer: A = d act0 (bf16), B gathered element-wise from the padded fp32 input
-        const ConvSpec& c0 = c.PL.conv[0];
+    // the stem's weight gradient where conv_1's data gradient did not take it: A = d act0 (bf16), B gathered element-wise from the padded fp32 input
+    if (c.stem_wgrad == STEM_WGRAD16) {
+        TRY(spair_stem_wgrad16_impl(c.w.dact[0], c.w.xpad, grads + c0.w, grads + c0.b, c.w.tn_part, SPAIR_TN_PART_FLOATS, d.B, c0.hin, c0.s,
+                                    c0.hout, c.s));
+    } else if (c.stem_wgrad == STEM_GENERIC) {
         const ConvDesc cd = fwd_desc(c0);
         const int K = c0.k * c0.k * c0.cin;
-        if (c0.cin == 1 && c0.k == 4 && c0.cout == 128) {
-            TRY(spair_stem_wgrad16_impl(c.w.dact[0], c.w.xpad, grads + c0.w, grads + c0.b, c.w.tn_part, SPAIR_TN_PART_FLOATS, d.B, c0.hin,
-                                        c0.s, c0.hout, c.s));
-        } else {
-            TRY(tn16(c, c.w.dact[0], c0.cout, c0.cout, c.w.xpad, 0, K, false, grads + c0.w, K, d.B * c0.hout * c0.hout, grads + c0.b, &cd,
-                     c0.cin, c0.k * c0.k));
-        }
+        TRY(tn16(c, c.w.dact[0], c0.cout, c0.cout, c.w.xpad, 0, K, false, grads + c0.w, K, d.B * c0.hout * c0.hout, grads + c0.b, &cd, c0.cin,
+                 c0.k * c0.k));
     }
     return SPAIR_OK;
 }
@@ -897,51 +933,29 @@ static int backbone_bwd(Ctx& c, float* grads) {
         const float* dout = (i == last) ? c.w.dfeat : c.w.dact[i];
         const int ldd = (i == last) ? c.w.ld_feat : cs.cout;
         const float* in = c.w.act[i - 1];
-        // weight + bias gradients
-        if (cs.k == 1) {
-            TRY(tn(c, dout, ldd, cs.cout, in, cs.cin, cs.cin, grads + cs.w, cs.cin, M, grads + cs.b));
-        } else {
-            GemmTN g;
-            memset(&g, 0, sizeof(g));
-            const int K = cs.k * cs.k * cs.cin;
-            g.A = dout; g.lda = ldd; g.B = in; g.C = grads + cs.w; g.ldc = K; g.M = round_up(cs.cout, 4); g.N = K; g.Mstore = cs.cout; g.Nstore = K;
-            g.R = M; g.cw_cin = cs.cin; g.cw_taps = cs.k * cs.k; g.conv = fwd_desc(cs); g.colsum_out = grads + cs.b;
-            TRY(spair_gemm_tn_impl(g, true, c.d.dtype, c.s));
-        }
-        // data gradient into dact[i-1] (masked by relu of act[i-1])
+        // weight + bias gradients, then the data gradient into dact[i-1] (masked by relu of act[i-1])
         if (cs.k == 1) {
             const int Kd = round_up(cs.cout, 8);
+            TRY(tn(c, dout, ldd, cs.cout, in, cs.cin, cs.cin, grads + cs.w, cs.cin, M, grads + cs.b));
             TRY(nt(c, dout, ldd, c.w.conv_wd[i][0], Kd, c.w.dact[i - 1], cs.cin, M, cs.cin, Kd, nullptr, in, cs.cin, 0));
-        } else {
-            const int T = cs.k / cs.s;
-            for (int py = 0; py < cs.s; ++py)
-                for (int px = 0; px < cs.s; ++px) {
-                    const int Hc = (cs.hin - py + cs.s - 1) / cs.s, Wc = (cs.hin - px + cs.s - 1) / cs.s;
-                    if (Hc <= 0 || Wc <= 0) continue;
-                    GemmNT g;
-                    memset(&g, 0, sizeof(g));
-                    g.A = dout; g.B = c.w.conv_wd[i][py * cs.s + px]; g.ldb = T * T * cs.cout; g.C = c.w.dact[i - 1]; g.ldc = cs.cin;
-                    g.M = d.B * Hc * Wc; g.N = cs.cin; g.K = T * T * cs.cout; g.mask = in; g.ldmask = cs.cin;
-                    g.conv.Hin = cs.hout; g.conv.Win = cs.hout; g.conv.Cin = cs.cout; g.conv.Hout = Hc; g.conv.Wout = Wc;
-                    g.conv.kh = T; g.conv.kw = T; g.conv.sy = 1; g.conv.sx = 1; g.conv.dky = -1; g.conv.dkx = -1; g.conv.oy = 0; g.conv.ox = 0;
-                    g.use_cmap = 1;
-                    g.cmap.Hout = Hc; g.cmap.Wout = Wc; g.cmap.Hc = cs.hin; g.cmap.Wc = cs.hin; g.cmap.osy = cs.s; g.cmap.osx = cs.s;
-                    g.cmap.ooy = py; g.cmap.oox = px;
-                    TRY(spair_gemm_nt_impl(g, true, d.dtype, c.s));
-                }
+            continue;
         }
+        const int K = cs.k * cs.k * cs.cin, T = cs.k / cs.s;
+        const ConvDesc cd = fwd_desc(cs);
+        TRY(tn(c, dout, ldd, cs.cout, in, 0, K, grads + cs.w, K, M, grads + cs.b, &cd, cs.cin, cs.k * cs.k));
+        for (int py = 0; py < cs.s; ++py)
+            for (int px = 0; px < cs.s; ++px) {
+                ConvDesc dd; RowMap rm;
+                const int rows = dgrad_class(cs, py, px, dd, rm);
+                if (rows) TRY(nt(c, dout, 0, c.w.conv_wd[i][py * cs.s + px], T * T * cs.cout, c.w.dact[i - 1], cs.cin, d.B * rows, cs.cin, T * T * cs.cout,
+                                 nullptr, in, cs.cin, 0, &dd, &rm));
+            }
     }
-    {   // first layer (Cin = image channels): the same TN GEMM, B gathered element-wise from the padded input
-        const ConvSpec& c0 = c.PL.conv[0];
-        GemmTN g;
-        memset(&g, 0, sizeof(g));
-        const int K = c0.k * c0.k * c0.cin;
-        g.A = c.w.dact[0]; g.lda = c0.cout; g.B = c.w.xpad; g.C = grads + c0.w; g.ldc = K; g.M = round_up(c0.cout, 4); g.N = round_up(K, 4);
-        g.Mstore = c0.cout; g.Nstore = K; g.R = d.B * c0.hout * c0.hout; g.cw_cin = c0.cin; g.cw_taps = c0.k * c0.k; g.conv = fwd_desc(c0);
-        g.colsum_out = grads + c0.b;
-        TRY(spair_gemm_tn_impl(g, true, c.d.dtype, c.s));
-    }
-    return SPAIR_OK;
+    // first layer (Cin = image channels): the same TN GEMM, B gathered element-wise from the padded input
+    const ConvSpec& c0 = c.PL.conv[0];
+    const ConvDesc cd = fwd_desc(c0);
+    const int K = c0.k * c0.k * c0.cin;
+    return tn(c, c.w.dact[0], c0.cout, c0.cout, c.w.xpad, 0, K, grads + c0.w, K, d.B * c0.hout * c0.hout, grads + c0.b, &cd, c0.cin, c0.k * c0.k);
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------
@@ -1136,12 +1150,12 @@ extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const 
     CellBufs& P = c.w.cb;
     P.z_where = z_where; P.z_pres = z_pres;
     SideStream* side = nullptr;
-    if (!(st->flags & 4)) TRY(side_stream(side));
+    if (c.use_side) TRY(side_stream(side));
     std::unique_lock<std::mutex> enq_lock;
     if (side) enq_lock = std::unique_lock<std::mutex>(side->enq_mu);
     {   // tables + per-step weight copies (helper stream) beside the input padding and the stem conv (caller's stream)
-        hipStream_t const main_s = c.s;
-        if (side) { TRY(stream_link(main_s, side->s, side->ev[2])); c.s = side->s; }
+        if (side) TRY(stream_link(c.s, side->s, side->ev[2]));
+        OnHelper on_helper(c, side);
         {
             ProfScope ps(PS_PREP, c.s);
             TRY(prep_weights(c, st->train != 0, 0));       // conv weights first: conv_1 waits for these only
@@ -1157,7 +1171,6 @@ extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const 
         // later joins order it before the backward)
         if (misc_conv0_reads_unpadded(d->B, c.PL.conv[0].hin, d->C, c.PL.conv[0].k, c.PL.conv[0].cout))
             TRY(misc_pad_input(x, c.w.xpad, d->B, d->C, d->I, d->pad_pre, d->I + d->pad_pre + d->pad_post, c.s));
-        c.s = main_s;
     }
     const int ps_bb = prof_begin(PS_BACKBONE_FWD, c.s);
     TRY(backbone_stem_fwd(c));
@@ -1307,7 +1320,7 @@ static int cells_wgrad_grouped(Ctx& c, float* grads) {
     add(LIN_OBJ2, P.dOo, L.ld_oo, 0, P.Ho2, SP_LDH);
     if (!fits) return SPAIR_ERR_UNSUPPORTED;
     g.ngroup = nt; g.R = L.N;
-    g.part = c.tn_scratch ? c.tn_scratch : c.w.tn_part; g.part_cap = SPAIR_TN_PART_FLOATS;
+    g.part = c.tn_part; g.part_cap = SPAIR_TN_PART_FLOATS;
     TRY(spair_gemm_tn16_impl(g, false, true, c.s));      // A and B both bf16 rows
     const LinSpec& e0 = c.PL.lin[LIN_ENC0];
     return tn16(c, P.dHe1, SP_ENC_H1, e0.out, P.glimpse, L.ld_gl, e0.in, true, grads + e0.w, e0.in, (int)L.N, grads + e0.b);
@@ -1329,13 +1342,11 @@ static int decoder_small_wgrad_grouped(Ctx& c, float* grads, long long N) {
             t.M = round_up(ms, 8); t.N = std::min(round_up(l.in, 8), ldi); t.Mstore = ms; t.Nstore = l.in; t.m_skip = 0; t.n_skip = 0;
         }
     };
-    if (l1.in > 128 || l0.in > 128 || (l1.out & 7) || (l0.out & 7) || ceil_div(l1.out, 128) + ceil_div(l0.out, 128) > SPAIR_TN_MAX_TILES)
-        return SPAIR_ERR_UNSUPPORTED;
+    if (!decoder_small_wgrad_grouped_supported(c)) return SPAIR_ERR_UNSUPPORTED;
     add(l1, c.w.dHd2, SP_DEC_H2, c.w.Hd1, SP_DEC_H1);
     add(l0, c.w.dHd1, SP_DEC_H1, c.w.Za16, c.L.ld_rec);
-    for (int q = 0; q < nt; ++q) if (g.tile[q].N < g.tile[q].Nstore) return SPAIR_ERR_UNSUPPORTED;
     g.ngroup = nt; g.R = (int)N;
-    g.part = c.tn_scratch ? c.tn_scratch : c.w.tn_part; g.part_cap = SPAIR_TN_PART_FLOATS;
+    g.part = c.tn_part; g.part_cap = SPAIR_TN_PART_FLOATS;
     return spair_gemm_tn16_impl(g, false, true, c.s);
 }
 
@@ -1355,6 +1366,25 @@ extern "C" int spair_grad_buckets(const SpairDims* d, int64_t* lo3, int64_t* hi3
 static int record_ready(void* ev, hipStream_t s) {
     if (ev && hipEventRecord((hipEvent_t)ev, s) != hipSuccess) return SPAIR_ERR_LAUNCH;
     return SPAIR_OK;
+}
+
+// the d-logits as the bf16 step's decoder backward reads them: bf16 (the generic-channel renderer's fp32 ones through the copy dLog16)
+static const void* dlog16(const Ctx& c) { return c.rp.g16 ? (const void*)c.w.dLog : c.w.dLog16; }
+// The bf16 step's decoder weight gradients on c.s, then ev_decoder.  With the fused chain and the helper stream (plan: dec_wgrad_late) they are
+// issued BEHIND the chain backward's launch (round 6): its 256 LDS-exclusive workgroups leave them no CU before they retire anyway, but issued
+// in front of it they were eligible the moment the first chain workgroup left -- and took the machine from the 1x1 stack's data gradient, the
+// head of the backbone backward's critical path, which only becomes eligible when the LAST chain workgroup has left.
+static int decoder_wgrads16(Ctx& c, float* grads, void* ev_decoder) {
+    const LinSpec &l2 = c.PL.lin[LIN_DEC2], &l1 = c.PL.lin[LIN_DEC1], &l0 = c.PL.lin[LIN_DEC0];
+    const int N = c.L.N;
+    { ProfScope p2(PS_DEC2_WGRAD, c.s); TRY(tn16(c, dlog16(c), c.w.ld_s, l2.out, c.w.Hd2, SP_DEC_H2, l2.in, true, grads + l2.w, l2.in, N, grads + l2.b)); }
+    if (c.dec_wgrad_grouped) {
+        TRY(decoder_small_wgrad_grouped(c, grads, N));
+    } else {
+        TRY(tn16(c, c.w.dHd2, SP_DEC_H2, l1.out, c.w.Hd1, SP_DEC_H1, l1.in, true, grads + l1.w, l1.in, N, grads + l1.b));
+        TRY(tn16(c, c.w.dHd1, SP_DEC_H1, l0.out, c.w.Za16, c.L.ld_rec, l0.in, true, grads + l0.w, l0.in, N, grads + l0.b));
+    }
+    return record_ready(ev_decoder, c.s);
 }
 
 extern "C" int spair_backward_ev(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
@@ -1391,12 +1421,11 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
                          const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
                          float* aux_scratch, float* grad_x, int bce_target, float* x_scratch) {
     Ctx c;
-    TRY(make_ctx(c, d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, stream));
+    TRY(make_ctx(c, d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, stream, grad_x != nullptr));
     if (!grad_loss || !grads) return SPAIR_ERR_SHAPE;
     if (grad_recon && (!inv_den || !aux_scratch)) return SPAIR_ERR_SHAPE;
     if (grad_x && (!x_scratch || c.PL.n_conv < 2)) return grad_x && !x_scratch ? SPAIR_ERR_SHAPE : SPAIR_ERR_UNSUPPORTED;
     if (grad_x && (size_t)c.PL.conv[0].cout * d->C * c.PL.conv[0].k * c.PL.conv[0].k * 4 > 65536) return SPAIR_ERR_UNSUPPORTED;
-    c.keep_dact0 = grad_x != nullptr;
     const CellLayout& L = c.L;
     CellBufs& P = c.w.cb;
     const ParamLayout& PL = c.PL;
@@ -1429,62 +1458,37 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
     // adjoints of the z_where / z_pres outputs: added to the rows the renderer just wrote, before the per-cell backward reads them
     TRY(outgrad_rows_fold(P.cell_h, P.cell_w, d->B, d->G, grad_z_where, grad_z_pres, P.g_nbox_r, P.g_pres_r, c.s));
     SideStream* side = nullptr;
-    if (!(st->flags & 4)) TRY(side_stream(side));
+    if (c.use_side) TRY(side_stream(side));
     std::unique_lock<std::mutex> enq_lock;
     if (side) enq_lock = std::unique_lock<std::mutex>(side->enq_mu);
-    hipStream_t const main_s = c.s;
-    std::function<int()> dec_wgrads;
     if (PL.oc_n) {
         ProfScope ps(PS_DECODER_BWD, c.s);
         TRY(oc_decoder_bwd(c, grads));
         TRY(record_ready(ev_decoder, c.s));
     } else if (b16) {   // decoder, bf16-stored activations and gradients: the data-gradient chain stays on the caller's stream, the three
                  // weight gradients go to the helper stream and overlap with the (latency-bound) per-cell backward chain
-        const LinSpec &l2 = PL.lin[LIN_DEC2], &l1 = PL.lin[LIN_DEC1], &l0 = PL.lin[LIN_DEC0];
-        float* const dlog_f32 = c.w.dLog;
-        if (!c.rp.g16) {      // the generic-channel renderer left fp32 sprite gradients
-            TRY(spair_to_bf16(c.w.dLog, c.w.ld_s, c.w.dLog16, c.w.ld_s, N, c.w.ld_s, c.s));
-            c.w.dLog = reinterpret_cast<float*>(c.w.dLog16);
-        }
+        const LinSpec& l0 = PL.lin[LIN_DEC0];
+        if (!c.rp.g16) TRY(spair_to_bf16(c.w.dLog, c.w.ld_s, c.w.dLog16, c.w.ld_s, N, c.w.ld_s, c.s));     // the generic-channel renderer left fp32 d-logits
+        const void* const dL = dlog16(c);
         {
             ProfScope ps(PS_DECODER_BWD, c.s);
-            // all three data gradients in one launch (dec_fused_bwd.hip); flags bit 6 / an unsupported shape: three implicit-GEMM launches
-            int rc_f = SPAIR_ERR_UNSUPPORTED;
-            if (!(st->flags & 64)) {
+            if (c.dec_dgrad_fused) {      // all three data gradients in one launch (dec_fused_bwd.hip)
                 ProfScope p2(PS_DEC2_DGRAD, c.s);
-                rc_f = dec_fused_bwd(c.w.dLog, c.w.ld_s, c.w.lin_wt[LIN_DEC2], round_up(per, 8), c.w.lin_wt[LIN_DEC1], c.w.lin_wt[LIN_DEC0], c.w.Hd2,
-                                     c.w.Hd1, c.w.dHd2, c.w.dHd1, P.g_attr_r, L.ld_rec, N, l0.in, per, c.s);
-                if (rc_f != SPAIR_OK && rc_f != SPAIR_ERR_UNSUPPORTED) return rc_f;
-            }
-            if (rc_f == SPAIR_ERR_UNSUPPORTED) {
-            { ProfScope p2(PS_DEC2_DGRAD, c.s);
-              TRY(nt16(c, c.w.dLog, c.w.ld_s, c.w.lin_wt[LIN_DEC2], round_up(per, 8), c.w.dHd2, SP_DEC_H2, 1, N, SP_DEC_H2, round_up(per, 8), nullptr,
-                       c.w.Hd2, SP_DEC_H2, 0)); }
-            TRY(nt16(c, c.w.dHd2, SP_DEC_H2, c.w.lin_wt[LIN_DEC1], SP_DEC_H2, c.w.dHd1, SP_DEC_H1, 1, N, SP_DEC_H1, SP_DEC_H2, nullptr, c.w.Hd1, SP_DEC_H1, 0));
-            TRY(nt16(c, c.w.dHd1, SP_DEC_H1, c.w.lin_wt[LIN_DEC0], SP_DEC_H1, P.g_attr_r, L.ld_rec, 0, N, l0.in, SP_DEC_H1, nullptr, nullptr, 0, 0));
+                TRY(dec_fused_bwd(dL, c.w.ld_s, c.w.lin_wt[LIN_DEC2], round_up(per, 8), c.w.lin_wt[LIN_DEC1], c.w.lin_wt[LIN_DEC0], c.w.Hd2, c.w.Hd1,
+                                  c.w.dHd2, c.w.dHd1, P.g_attr_r, L.ld_rec, N, l0.in, per, c.s));
+            } else {
+                { ProfScope p2(PS_DEC2_DGRAD, c.s);
+                  TRY(nt16(c, dL, c.w.ld_s, c.w.lin_wt[LIN_DEC2], round_up(per, 8), c.w.dHd2, SP_DEC_H2, 1, N, SP_DEC_H2, round_up(per, 8), nullptr,
+                           c.w.Hd2, SP_DEC_H2, 0)); }
+                TRY(nt16(c, c.w.dHd2, SP_DEC_H2, c.w.lin_wt[LIN_DEC1], SP_DEC_H2, c.w.dHd1, SP_DEC_H1, 1, N, SP_DEC_H1, SP_DEC_H2, nullptr, c.w.Hd1, SP_DEC_H1, 0));
+                TRY(nt16(c, c.w.dHd1, SP_DEC_H1, c.w.lin_wt[LIN_DEC0], SP_DEC_H1, P.g_attr_r, L.ld_rec, 0, N, l0.in, SP_DEC_H1, nullptr, nullptr, 0, 0));
             }
         }
-        // The decoder's three weight gradients (helper stream).  With the fused chain they are issued BEHIND the chain backward's launch (round 6):
-        // its 256 LDS-exclusive workgroups leave them no CU before they retire anyway, but issued in front of it they were eligible the moment
-        // the first chain workgroup left -- and took the machine from the 1x1 stack's data gradient, the head of the backbone backward's
-        // critical path, which only becomes eligible when the LAST chain workgroup has left.
-        float* const dlog_w = c.w.dLog;
-        dec_wgrads = [&c, &l2, &l1, &l0, &L, grads, N, dlog_w, ev_decoder]() -> int {
-            { ProfScope p2(PS_DEC2_WGRAD, c.s); TRY(tn16(c, dlog_w, c.w.ld_s, l2.out, c.w.Hd2, SP_DEC_H2, l2.in, true, grads + l2.w, l2.in, N, grads + l2.b)); }
-            const int rc_g = decoder_small_wgrad_grouped(c, grads, N);
-            if (rc_g == SPAIR_ERR_UNSUPPORTED) {
-                TRY(tn16(c, c.w.dHd2, SP_DEC_H2, l1.out, c.w.Hd1, SP_DEC_H1, l1.in, true, grads + l1.w, l1.in, N, grads + l1.b));
-                TRY(tn16(c, c.w.dHd1, SP_DEC_H1, l0.out, c.w.Za16, L.ld_rec, l0.in, true, grads + l0.w, l0.in, N, grads + l0.b));
-            } else if (rc_g != SPAIR_OK) return rc_g;
-            return record_ready(ev_decoder, c.s);
-        };
-        if (!(side && c.use_chain)) {          // no helper stream / per-wavefront launches: where they always were
-            if (side) { TRY(stream_link(main_s, side->s, side->ev[0])); c.s = side->s; c.tn_scratch = c.w.tn_part2; }
-            TRY(dec_wgrads());
-            dec_wgrads = nullptr;
-            if (side) { c.s = main_s; c.tn_scratch = nullptr; }
+        if (!c.dec_wgrad_late) {      // no helper stream / per-wavefront launches: the weight gradients right here
+            if (side) TRY(stream_link(c.s, side->s, side->ev[0]));
+            OnHelper on_helper(c, side);
+            TRY(decoder_wgrads16(c, grads, ev_decoder));
         }
-        c.w.dLog = dlog_f32;
     } else {   // decoder
         ProfScope ps(PS_DECODER_BWD, c.s);
         { ProfScope p2(PS_DEC2_WGRAD, c.s); TRY(wgrad_lin(c, LIN_DEC2, c.w.dLog, c.w.ld_s, c.w.Hd2, SP_DEC_H2, grads, N)); }
@@ -1538,58 +1542,51 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
     TRY(cells_dfeat_edge(L, P, grads + PL.edge, c.s));
     }
     prof_end(ps_cells, c.s);
-    // the per-cell weight gradients (helper stream) and the backbone backward (caller's stream) both hang off the chain only
-    if (side) { TRY(stream_link(main_s, side->s, side->ev[2])); c.s = side->s; }
-    if (dec_wgrads) {                          // (deferred: see the decoder block)
-        c.tn_scratch = c.w.tn_part2;
-        TRY(dec_wgrads());
-        c.tn_scratch = nullptr;
-    }
-    const int ps_wg = prof_begin(PS_CELLS_WGRAD, c.s);
-    // weight gradients of the per-cell nets: long-K GEMMs over all N rows
-    if (c.use_chain) {
-        if (side) c.tn_scratch = c.w.tn_part2;
-        TRY(cells_wgrad_grouped(c, grads));
-        c.tn_scratch = nullptr;
-        TRY(chain_edge_reduce(chain_args, c.s));       // the edge element's gradient: per-sample partials summed in sample order (off the critical path)
-    } else {
-    TRY(wgrad_lin(c, LIN_BOX0, P.dHb1, SP_LDH, P.Xb, L.ld_xb, grads, N));
-    TRY(wgrad_lin(c, LIN_BOX1, P.dHb2, SP_LDH, P.Hb1, SP_LDH, grads, N));
-    TRY(wgrad_lin(c, LIN_BOXH1, P.dOb, L.ld_ob, P.Hb2, SP_LDH, grads, N));
-    TRY(wgrad_lin(c, LIN_BOXH0, P.dOb + L.ob_lat, L.ld_ob, P.Hb2, SP_LDH, grads, N));
-    if (PL.oc_n) TRY(oc_encoder_wgrad(c, grads));
-    else {
-    TRY(wgrad_lin(c, LIN_ENC0, P.dHe1, SP_ENC_H1, P.glimpse, L.ld_gl, grads, N));
-    TRY(wgrad_lin(c, LIN_ENC1, P.dHe2, SP_ENC_H2, P.He1, SP_ENC_H1, grads, N));
-    TRY(wgrad_lin(c, LIN_ENC2, P.dOe, L.ld_oe, P.He2, SP_ENC_H2, grads, N));
-    }
-    TRY(wgrad_lin(c, LIN_Z0, P.dHz1, SP_LDH, P.Xz, L.ld_x, grads, N));
-    TRY(wgrad_lin(c, LIN_Z1, P.dHz2, SP_LDH, P.Hz1, SP_LDH, grads, N));
-    TRY(wgrad_lin(c, LIN_ZH1, P.dOz, L.ld_oz, P.Hz2, SP_LDH, grads, N));
-    TRY(wgrad_lin(c, LIN_ZH0, P.dOz + L.oz_lat, L.ld_oz, P.Hz2, SP_LDH, grads, N));
-    TRY(wgrad_lin(c, LIN_OBJ0, P.dHo1, SP_LDH, P.Xo, L.ld_x, grads, N));
-    TRY(wgrad_lin(c, LIN_OBJ1, P.dHo2, SP_LDH, P.Ho1, SP_LDH, grads, N));
-    TRY(wgrad_lin(c, LIN_OBJ2, P.dOo, L.ld_oo, P.Ho2, SP_LDH, grads, N));
-    }
-    prof_end(ps_wg, c.s);
-    TRY(record_ready(ev_cells, c.s));
-    if (side) {
-        if (hipEventRecord(side->ev[3], side->s) != hipSuccess) return SPAIR_ERR_LAUNCH;
-        c.s = main_s;
+    {   // the per-cell weight gradients (helper stream) and the backbone backward (caller's stream) both hang off the chain only
+        if (side) TRY(stream_link(c.s, side->s, side->ev[2]));
+        OnHelper on_helper(c, side);
+        if (c.dec_wgrad_late) TRY(decoder_wgrads16(c, grads, ev_decoder));      // (see decoder_wgrads16)
+        const int ps_wg = prof_begin(PS_CELLS_WGRAD, c.s);
+        // weight gradients of the per-cell nets: long-K GEMMs over all N rows
+        if (c.use_chain) {
+            TRY(cells_wgrad_grouped(c, grads));
+            TRY(chain_edge_reduce(chain_args, c.s));       // the edge element's gradient: per-sample partials summed in sample order (off the critical path)
+        } else {
+        TRY(wgrad_lin(c, LIN_BOX0, P.dHb1, SP_LDH, P.Xb, L.ld_xb, grads, N));
+        TRY(wgrad_lin(c, LIN_BOX1, P.dHb2, SP_LDH, P.Hb1, SP_LDH, grads, N));
+        TRY(wgrad_lin(c, LIN_BOXH1, P.dOb, L.ld_ob, P.Hb2, SP_LDH, grads, N));
+        TRY(wgrad_lin(c, LIN_BOXH0, P.dOb + L.ob_lat, L.ld_ob, P.Hb2, SP_LDH, grads, N));
+        if (PL.oc_n) TRY(oc_encoder_wgrad(c, grads));
+        else {
+        TRY(wgrad_lin(c, LIN_ENC0, P.dHe1, SP_ENC_H1, P.glimpse, L.ld_gl, grads, N));
+        TRY(wgrad_lin(c, LIN_ENC1, P.dHe2, SP_ENC_H2, P.He1, SP_ENC_H1, grads, N));
+        TRY(wgrad_lin(c, LIN_ENC2, P.dOe, L.ld_oe, P.He2, SP_ENC_H2, grads, N));
+        }
+        TRY(wgrad_lin(c, LIN_Z0, P.dHz1, SP_LDH, P.Xz, L.ld_x, grads, N));
+        TRY(wgrad_lin(c, LIN_Z1, P.dHz2, SP_LDH, P.Hz1, SP_LDH, grads, N));
+        TRY(wgrad_lin(c, LIN_ZH1, P.dOz, L.ld_oz, P.Hz2, SP_LDH, grads, N));
+        TRY(wgrad_lin(c, LIN_ZH0, P.dOz + L.oz_lat, L.ld_oz, P.Hz2, SP_LDH, grads, N));
+        TRY(wgrad_lin(c, LIN_OBJ0, P.dHo1, SP_LDH, P.Xo, L.ld_x, grads, N));
+        TRY(wgrad_lin(c, LIN_OBJ1, P.dHo2, SP_LDH, P.Ho1, SP_LDH, grads, N));
+        TRY(wgrad_lin(c, LIN_OBJ2, P.dOo, L.ld_oo, P.Ho2, SP_LDH, grads, N));
+        }
+        prof_end(ps_wg, c.s);
+        TRY(record_ready(ev_cells, c.s));
+        if (side && hipEventRecord(side->ev[3], side->s) != hipSuccess) return SPAIR_ERR_LAUNCH;
     }
     { ProfScope ps(PS_BACKBONE_BWD, c.s); TRY(backbone_bwd(c, grads)); }
-    if (side && hipStreamWaitEvent(main_s, side->ev[3], 0) != hipSuccess) return SPAIR_ERR_LAUNCH;      // join
-    TRY(record_ready(ev_backbone, main_s));
+    if (side && hipStreamWaitEvent(c.s, side->ev[3], 0) != hipSuccess) return SPAIR_ERR_LAUNCH;      // join
+    TRY(record_ready(ev_backbone, c.s));
     if (grad_x) {     // behind ev_backbone: the gradient buckets are not delayed
         if (c.use_chain) {      // the fused chain keeps dHe1 (bf16) but not dGl: one 16-bit NT GEMM, as bwd_lin does per wavefront
             const LinSpec& e0 = PL.lin[LIN_ENC0];
             const int K = round_up(e0.out, 8);
             TRY(nt16(c, P.dHe1, SP_ENC_H1, c.w.lin_wt[LIN_ENC0], K, P.dGl, L.ld_gl, 0, N, e0.in, K, nullptr, nullptr, 0, 0));
         }
-        TRY(input_grad_glimpse(P.nbox, d->B, d->G * d->G, P.dGl, L.ld_gl, x_scratch, d->C, d->I, d->P, d->align_corners, main_s));
+        TRY(input_grad_glimpse(P.nbox, d->B, d->G * d->G, P.dGl, L.ld_gl, x_scratch, d->C, d->I, d->P, d->align_corners, c.s));
         const ConvSpec& c0 = PL.conv[0];
         TRY(input_grad_stem(c.w.dact[0], b16, params + c0.w, d->B, d->C, d->I, d->pad_pre, c0.k, c0.s, c0.hout, c0.cout, x_scratch, c.w.aux,
-                            bce_target ? grad_loss : nullptr, grad_x, main_s));
+                            bce_target ? grad_loss : nullptr, grad_x, c.s));
     }
     return SPAIR_OK;
 }
@@ -1624,19 +1621,26 @@ extern "C" int spair_chain_stamps(const SpairDims* d, const void* workspace, uns
 
 static_assert(SPAIR_RENDER_MMA == RENDER_MMA && SPAIR_RENDER_GEN2 == RENDER_GEN2 && SPAIR_RENDER_GEN1 == RENDER_GEN1 &&
               SPAIR_RENDER_COLOUR == RENDER_COLOUR, "include/spair_hip.h names the RenderFamily values");
-// diagnostic: the kernel plan make_ctx computes for these dims, workspace and SpairStep.flags (host only: nothing launched, nothing read)
-extern "C" int spair_step_plan(const SpairDims* d, const void* workspace, int flags, int* out) {
+static_assert(SPAIR_STEP_PLAN_INTS == 14 + 3 * SP_MAX_CONV, "include/spair_hip.h lays out spair_step_plan_n");
+// diagnostic: the kernel plan make_ctx computes for these dims, workspace, SpairStep.flags and input gradient (host only: nothing launched,
+// nothing read)
+extern "C" int spair_step_plan_n(const SpairDims* d, const void* workspace, int flags, int input_grad, int* out, int n) {
     if (!d || !workspace || !out) return SPAIR_ERR_SHAPE;
     TRY(validate(*d));
     Ctx c;
-    c.d = *d;
-    c.L = make_cell_layout(*d);
-    c.PL = make_param_layout(*d);
-    c.w = carve(*d, const_cast<void*>(workspace));
-    plan_step(c, flags);
-    const int v[8] = {c.rp.fwd, c.rp.bwd, c.rp.rec, c.rp.s16, c.rp.g16, c.use_chain, c.use_dec_fused, 0};
-    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    c.d = *d; c.L = make_cell_layout(*d); c.PL = make_param_layout(*d); c.w = carve(*d, const_cast<void*>(workspace));
+    plan_step(c, flags, input_grad != 0);
+    int v[SPAIR_STEP_PLAN_INTS] = {c.rp.fwd, c.rp.bwd, c.rp.rec, c.rp.s16, c.rp.g16, c.use_chain, c.use_dec_fused, 0,
+                                   c.use_side, c.dec_dgrad_fused, c.dec_wgrad_grouped, c.dec_wgrad_late, c.pw0, c.stem_wgrad};
+    for (int i = 1; i <= SP_MAX_CONV; ++i) {      // per layer: forward, data gradient, gate bits (-1 past conv_out)
+        const bool on = i < c.PL.n_conv;
+        v[13 + i] = on ? c.conv_fwd[i] : -1; v[21 + i] = on ? c.conv_dgrad[i] : -1; v[29 + i] = on ? c.dgrad_bits[i] != nullptr : -1;
+    }
+    for (int i = 0; i < std::min(n, SPAIR_STEP_PLAN_INTS); ++i) out[i] = v[i];
     return SPAIR_OK;
+}
+extern "C" int spair_step_plan(const SpairDims* d, const void* workspace, int flags, int* out) {
+    return spair_step_plan_n(d, workspace, flags, 0, out, 8);
 }
 
 // band split of the fused chain kernels: 1 if a wait for the neighbouring band ever timed out in a launch on this workspace (STICKY: no

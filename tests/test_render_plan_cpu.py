@@ -1,8 +1,11 @@
-"""The kernel plan of the training step (spair_step_plan: the host arithmetic make_ctx runs -- render_plan, chain_fwd_supported,
-dec_fused_supported) for the configurations the suite covers.  CPU only: the workspace is an address that is never dereferenced.
+"""The kernel plan of the training step (spair_step_plan / spair_step_plan_n: the host arithmetic make_ctx runs -- render_plan,
+chain_fwd_supported, dec_fused_supported, the backbone's and the decoder backward's predicates) for the configurations the suite covers.
+CPU only: the workspace is an address that is never dereferenced.
 
 A predicate edit that moves one of these configurations to another renderer family, turns the fused chain or the fused decoder on or
-off, or changes a sprite / d-logit format fails here; tests/test_object_geometry_gpu.py runs each of them against the oracle."""
+off, or changes a sprite / d-logit format fails here; tests/test_object_geometry_gpu.py runs each of them against the oracle.  The same
+holds for the backbone's kernels per layer, the gate each data gradient reads, where the stem's weight gradient is taken, and the decoder
+backward's kernels and stream."""
 import pytest
 
 WS = 1 << 30          # a 256-byte-aligned fake workspace base (the workspace's buffers share its alignment)
@@ -82,3 +85,84 @@ def test_step_plan_refuses_what_the_engine_refuses():
         L.step_plan(d, WS)
     with pytest.raises(L.SpairHipError, match="code -1"):
         L.step_plan(dims("bf16", 1, 28, 0, 48, 4), 0)
+
+
+# spair_step_plan_n: the default topology's layers 1 .. 6 are conv_1, conv_2 (4x4, stride 2 here) and four 1x1 layers (conv_3 .. conv_out),
+# which run as the fused 1x1 stack in the bf16 step
+PW4 = ("PW_STACK",) * 4
+
+
+def expect_n(fwd=("PATCH", "PATCH"), dgrad=("PATCH", "PATCH"), bits=(True, True), stem="PATCH", side=True, dec_dgrad_fused=True,
+             dec_wgrad_grouped=True, dec_wgrad_late=True):
+    return dict(side=side, dec_dgrad_fused=dec_dgrad_fused, dec_wgrad_grouped=dec_wgrad_grouped, dec_wgrad_late=dec_wgrad_late, pw0=3,
+                stem=stem, fwd=tuple(fwd) + PW4, dgrad=tuple(dgrad) + PW4, gate_bits=tuple(bits) + (False,) * 4)
+
+
+BENCH = expect_n()      # patch-resident conv_1 / conv_2 both ways, their gates as sign bits, the stem's weight gradient in conv_1's dgrad
+# fp32: no 1x1 stack (pw0 = n_conv + 1), the per-class data gradient of the strided layers, the stem's weight gradient as a TN GEMM
+F32 = dict(expect_n(stem="GENERIC", dec_dgrad_fused=False, dec_wgrad_grouped=False, dec_wgrad_late=False), pw0=7, fwd=("GEMM",) * 6,
+           dgrad=("PER_CLASS", "PER_CLASS") + ("GEMM",) * 4, gate_bits=(False,) * 6)
+S11 = (3, 2, 2, 1, 1, 1)
+# (dtype, C, I, B, strides, flags, input_grad) -> plan
+PLANS_N = {
+    ("bf16", 1, 128, 32, STRIDES, 0, 0): BENCH,
+    ("bf16", 1, 48, 4, STRIDES, 0, 0): BENCH,
+    ("bf16", 1, 256, 1, STRIDES, 0, 0): BENCH,
+    # the reference's 11 x 11 grid: stride-3 stem (no sign bits; the fused stem needs an even stride), conv_1's patch dgrad without it
+    ("bf16", 1, 128, 32, S11, 0, 0): expect_n(bits=(False, True), stem="WGRAD16"),
+    ("bf16", 1, 128, 8, S11, 0, 1): expect_n(bits=(False, True), stem="WGRAD16"),
+    # an image gradient keeps d act0 in HBM: no stem fusion
+    ("bf16", 1, 128, 32, STRIDES, 0, 1): expect_n(stem="WGRAD16"),
+    ("f32", 1, 48, 4, STRIDES, 0, 0): F32,
+    ("f32", 1, 128, 2, STRIDES, 0, 1): F32,
+    # SpairStep.flags: bit 0 no fused chain (the decoder's weight gradients at once), bit 2 no helper stream, bit 3 no stem fusion, bit 5 no
+    # patch-resident kernels (the stem fused into conv_1's implicit-GEMM dgrad instead), bit 6 the decoder's data gradients as three GEMMs
+    ("bf16", 1, 128, 32, STRIDES, 1, 0): expect_n(dec_wgrad_late=False),
+    ("bf16", 1, 128, 32, STRIDES, 4, 0): expect_n(side=False, dec_wgrad_late=False),
+    ("bf16", 1, 128, 32, STRIDES, 8, 0): expect_n(stem="WGRAD16"),
+    ("bf16", 1, 128, 32, STRIDES, 32, 0): expect_n(fwd=("GEMM", "GEMM"), dgrad=("GEMM", "GEMM"), bits=(False, False), stem="GEMM"),
+    ("bf16", 1, 128, 32, STRIDES, 40, 0): expect_n(fwd=("GEMM", "GEMM"), dgrad=("GEMM", "GEMM"), bits=(False, False), stem="WGRAD16"),
+    ("bf16", 1, 128, 32, STRIDES, 64, 0): expect_n(dec_dgrad_fused=False),
+    ("bf16", 1, 48, 4, STRIDES, 4 | 8 | 64, 0): expect_n(side=False, stem="WGRAD16", dec_dgrad_fused=False, dec_wgrad_late=False),
+    # conv_1's input past the patch kernels' 32-bit offsets (B Hin^2 128 >= 2^31): its implicit-GEMM forward / class-batched dgrad, too
+    # many tiles for the fused stem; conv_2 keeps the patch kernels, its gate as the activation
+    ("bf16", 1, 128, 3600, STRIDES, 0, 0): expect_n(fwd=("GEMM", "PATCH"), dgrad=("GEMM", "PATCH"), bits=(False, False), stem="WGRAD16"),
+    # colour: the generic-channel stem (no sign bits), the decoder's weight gradients at once (no fused chain)
+    ("bf16", 3, 48, 4, STRIDES, 0, 0): expect_n(bits=(False, True), stem="GENERIC", dec_wgrad_late=False),
+}
+
+
+@pytest.mark.parametrize("key", list(PLANS_N), ids=lambda k: "%s-C%d-I%d-B%d-s%d-f%d-x%d" % (k[:4] + (k[4][0],) + k[5:]))
+def test_step_plan_n(key):
+    from spair_pytorch_amd import _lib as L
+    dtype, C, I, B, strides, flags, input_grad = key
+    assert L.step_plan_n(dims(dtype, C, 28, 0, I, B, strides=strides), WS, flags, input_grad) == PLANS_N[key]
+
+
+def test_step_plan_n_odd_conv1_input():
+    """Two more padding columns make conv_1's input odd (71 x 71 for 34 x 34 out): no patch kernel, the per-class data gradient, the stem's
+    weight gradient on its own; conv_2 keeps the patch kernels but gates with the activation (conv_1 left no sign bits)."""
+    from spair_pytorch_amd import _lib as L
+    d = dims("bf16", 1, 28, 0, 128, 4)
+    d.pad_post += 2
+    assert L.step_plan_n(d, WS) == expect_n(fwd=("GEMM", "PATCH"), dgrad=("PER_CLASS", "PATCH"), bits=(False, False), stem="WGRAD16")
+
+
+def test_step_plan_n_conv_object_nets():
+    """The convolutional object decoder: none of the MLP decoder's backward kernels; the backbone as with the MLP nets."""
+    from spair_pytorch_amd import _lib as L
+    assert L.step_plan_n(dims("bf16", 1, 28, 0, 48, 4, object_conv=True), WS) == expect_n(dec_dgrad_fused=False, dec_wgrad_grouped=False,
+                                                                                         dec_wgrad_late=False)
+
+
+def test_step_plan_is_the_head_of_step_plan_n():
+    """spair_step_plan writes the first 8 ints of spair_step_plan_n; spair_step_plan_n writes min(n, SPAIR_STEP_PLAN_INTS) of them."""
+    import ctypes
+    from spair_pytorch_amd import _lib as L
+    d = ctypes.byref(dims("bf16", 1, 28, 1, 64, 4))
+    full, head, part = (ctypes.c_int * L.STEP_PLAN_INTS)(), (ctypes.c_int * 8)(), (ctypes.c_int * L.STEP_PLAN_INTS)(*[-7] * L.STEP_PLAN_INTS)
+    L.check(L.lib().spair_step_plan_n(d, ctypes.c_void_p(WS), 16, 0, full, L.STEP_PLAN_INTS), "spair_step_plan_n")
+    L.check(L.lib().spair_step_plan(d, ctypes.c_void_p(WS), 16, head), "spair_step_plan")
+    L.check(L.lib().spair_step_plan_n(d, ctypes.c_void_p(WS), 16, 0, part, 10), "spair_step_plan_n")
+    assert list(head) == list(full)[:8] and full[7] == 0
+    assert list(part) == list(full)[:10] + [-7] * (L.STEP_PLAN_INTS - 10)
