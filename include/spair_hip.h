@@ -57,7 +57,18 @@ typedef struct SpairDims {
      * the learned edge element.  0 is read as 1 (the reference's configuration: UL, U, UR, L).  L != 1 runs on the per-wavefront
      * launches (dependency wavefronts t = (L+1) h + w); the fused per-cell kernels are built for L = 1.  1 <= L <= 3. */
     int lookback;
+    /* Rectangular images (appended; 0 = "same as the square fields", so a zero-initialised tail keeps the square meaning).  With them I, G
+     * and pad_post are the HEIGHT axis: the image is I x Iw pixels, the grid Gh x Gw = G x Gw cells, the padded frame
+     * (pad_pre + I + pad_post) x (pad_pre + Iw + pad_post_w).  pad_pre and cell_px are shared (square kernels and strides).  A rectangular
+     * image (Iw != I) runs on the per-wavefront launches, the implicit-GEMM / per-class backbone convolutions and the first-generation
+     * (grey) or generic-channel (colour) renderer: the kernel plan refuses every square-only specialisation.  G * Gw + 1 <= 1025;
+     * lookback > 1 needs max(G, Gw) <= 32. */
+    int Iw, Gw, pad_post_w;
 } SpairDims;
+
+/* Version of the layouts of SpairDims and SpairStep (and of the entry points' argument lists): a binding checks it before it passes a struct. */
+#define SPAIR_ABI_VERSION 2
+int spair_abi_version(void);
 
 /* Per-step scalars (host side evaluates the two schedules, modules.py:191-213). */
 typedef struct SpairStep {
@@ -101,8 +112,8 @@ int64_t spair_workspace_bytes(const SpairDims* d);
  *   loss_out (>= 10 floats): [0]=total, [1]=BCE sum, [2..8]=KL cy,cx,height,width,attr,depth,pres (batch means), [9]=total again (a
  *   second copy for a host layer that hands the loss out as a view: an in-place op on it then leaves the logged terms [0..8] alone).
  * backward == loss.backward() (train.py:66): accumulates into `grads` (same layout as params).
- * Noise maps are NCHW: eps_box[B,4,G,G] (cy,cx,height,width), eps_attr[B,A,G,G],
- * eps_depth[B,1,G,G], u_pres[B,1,G,G]. */
+ * Noise maps are NCHW: eps_box[B,4,G,Gw] (cy,cx,height,width), eps_attr[B,A,G,Gw],
+ * eps_depth[B,1,G,Gw], u_pres[B,1,G,Gw]; x and recon [B,C,I,Iw]; z_where [B,4,G,Gw], z_pres [B,1,G,Gw]. */
 int spair_forward(const SpairDims* d, const SpairStep* st, const float* params, const float* x,
                   const float* eps_box, const float* eps_attr, const float* eps_depth, const float* u_pres,
                   void* workspace, float* loss_out, float* recon, float* z_where, float* z_pres, void* stream);
@@ -119,11 +130,11 @@ int spair_backward_ev(const SpairDims* d, const SpairStep* st, const float* para
                       void* workspace, const float* grad_loss, float* grads, void* stream,
                       void* ev_decoder, void* ev_cells, void* ev_backbone);
 /* Differentiable outputs (the reference returns recon, z_where and z_pres as autograd tensors, models.py:35-131, so a user term on any of
- * them trains through the model).  spair_forward_out is spair_forward that also keeps inv_den [B][I][I] (1/D of the renderer's composite per
+ * them trains through the model).  spair_forward_out is spair_forward that also keeps inv_den [B][I][Iw] (1/D of the renderer's composite per
  * pixel; NULL = not kept).  spair_backward_out is spair_backward_ev that also folds the adjoints of the three outputs into the reverse pass:
- * grad_recon [B,C,I,I] (needs the inv_den of the same forward, else SPAIR_ERR_SHAPE), grad_z_where [B,4,G,G], grad_z_pres [B,1,G,G]; any of
+ * grad_recon [B,C,I,Iw] (needs the inv_den of the same forward, else SPAIR_ERR_SHAPE), grad_z_where [B,4,G,Gw], grad_z_pres [B,1,G,Gw]; any of
  * them may be NULL, and one that is NULL launches nothing (all three NULL = spair_backward_ev, kernel for kernel).  grad_loss may point at a
- * zero for a backward through the outputs alone.  aux_scratch: 2*B*C*I*I + 1 floats, only touched with grad_recon (the workspace keeps
+ * zero for a backward through the outputs alone.  aux_scratch: 2*B*C*I*Iw + 1 floats, only touched with grad_recon (the workspace keeps
  * what the forward saved, so a second backward through the same forward is unaffected).  Element for element, no atomics: deterministic. */
 int spair_forward_out(const SpairDims* d, const SpairStep* st, const float* params, const float* x,
                       const float* eps_box, const float* eps_attr, const float* eps_depth, const float* u_pres,
@@ -134,7 +145,7 @@ int spair_backward_out(const SpairDims* d, const SpairStep* st, const float* par
                        void* ev_decoder, void* ev_cells, void* ev_backbone,
                        const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
                        float* aux_scratch);
-/* spair_backward_x: spair_backward_out that also writes the gradient of the step with respect to its input image into grad_x [B,C,I,I]
+/* spair_backward_x: spair_backward_out that also writes the gradient of the step with respect to its input image into grad_x [B,C,I,Iw]
  * (OVERWRITTEN, fp32): the backbone term (the stem's data gradient from d act0), the glimpse term (the adjoint of the border-padded STN
  * glimpse) and, with bce_target != 0, the BCE-target term *grad_loss * (log1p(-recon) - log(recon)) -- torch's gradient of
  * binary_cross_entropy with respect to its target, not clamped: +inf where recon == 0, -inf where recon == 1 (the status word is not
@@ -162,7 +173,7 @@ int spair_adam_guarded(float* params, const float* grads, float* exp_avg, float*
 /* One int of host memory that kernels can store to (hipHostMalloc, mapped + coherent), zero-initialised: SpairStep.status_host. */
 int spair_host_word_alloc(int** out);
 int spair_host_word_free(int* word);
-/* Copy a per-row quantity of the last forward into an NCHW map [B,ch,G,G].
+/* Copy a per-row quantity of the last forward into an NCHW map [B,ch,G,Gw].
  * which: 0 z_attr, 1 z_depth, 2..7 mean of cy,cx,height,width,attr,depth, 8..13 their sigma, 14 count-prior p_z;
  * after a backward, its per-cell latent gradients: 100 d box head latents [8] (mean 4 | log-std 4), 101 d encoder output [2A], 102 d depth
  * latents [2], 103 d presence logit [1] as the per-wavefront launches store them (fp32 rows); 200..203 the same as the fused chain stores
@@ -209,6 +220,7 @@ int spair_chain_stamp_wavefronts(const SpairDims* d);
  * spair_forward / spair_backward on this workspace (sticky: only re-zeroing the workspace clears it; from that step on loss_out[0] and the
  * gradient of virtual_edge_element are NaN, so a training loop sees it without calling this), 0 if not, -1 where the kernels run unsplit */
 int spair_chain_sync_status(const SpairDims* d, const void* workspace, int* out, void* stream);
+/* the four noise maps [B,{4,A,1,1},G,Gw] of one step from a Philox stream */
 int spair_noise_fill(const SpairDims* d, uint64_t seed, float* eps_box, float* eps_attr, float* eps_depth, float* u_pres, void* stream);
 
 /* Opt-in instrumentation for bench.py: HIP events on the caller's stream around regions of the step.

@@ -17,6 +17,7 @@ _ERR = {-1: "bad shape", -2: "unsupported dtype", -3: "kernel launch failed", -4
         -5: "misaligned leading dimension / size"}
 
 _lib = None
+ABI_VERSION = 2          # SPAIR_ABI_VERSION (include/spair_hip.h)
 
 
 class SpairHipError(RuntimeError):
@@ -30,7 +31,14 @@ def lib():
             raise SpairHipError(
                 "libspair_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `python -m spair_pytorch_amd._build`. There is no CPU/PyTorch fallback." % LIB_PATH)
-        _lib = ctypes.CDLL(LIB_PATH)
+        h = ctypes.CDLL(LIB_PATH)
+        # the structs this package passes (models.SpairDims / SpairStep) must be the ones the library reads: a stale build with a shorter
+        # SpairDims would read past the end of the caller's struct
+        got = h.spair_abi_version() if hasattr(h, "spair_abi_version") else None
+        if got != ABI_VERSION:
+            raise SpairHipError("%s has ABI version %s, this package needs %d: rebuild it (python -m spair_pytorch_amd._build)"
+                                % (LIB_PATH, got, ABI_VERSION))
+        _lib = h
     return _lib
 
 

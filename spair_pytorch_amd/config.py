@@ -76,8 +76,10 @@ ALIGN_CORNERS = False
 OBJECT_ENCODER = os.environ.get('SPAIR_OBJECT_ENCODER', 'mlp')
 
 
-def set_grid(image_side, strides):
-    """Convenience for non-default geometries (e.g. 8-px cells: strides [2,2,2,1,1,1])."""
-    INPUT_IMAGE_SHAPE[1] = INPUT_IMAGE_SHAPE[2] = int(image_side)
+def set_grid(image_side, strides, image_width=None):
+    """Convenience for non-default geometries (e.g. 8-px cells: strides [2,2,2,1,1,1]).  ``image_side`` is the image height; the width is
+    ``image_width``, or the same (a square image) when it is None."""
+    INPUT_IMAGE_SHAPE[1] = int(image_side)
+    INPUT_IMAGE_SHAPE[2] = int(image_side if image_width is None else image_width)
     for layer, s in zip(DEFAULT_BACKBONE_TOPOLOGY, strides):
         layer['stride'] = int(s)

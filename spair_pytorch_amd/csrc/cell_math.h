@@ -37,10 +37,10 @@ __device__ __forceinline__ BoxFwd box_forward(const float* lat, const float* eps
     const float height = rhw * sigmoidf_(clamp10(z[2])) + H.min_hw;
     const float width = rhw * sigmoidf_(clamp10(z[3])) + H.min_hw;
     o.box[0] = cell_x; o.box[1] = cell_y; o.box[2] = width; o.box[3] = height;
-    o.nbox[3] = height * H.anchor / H.img;                    // ys
-    o.nbox[2] = width * H.anchor / H.img;                     // xs
+    o.nbox[3] = height * H.anchor / H.img;                    // ys (image height)
+    o.nbox[2] = width * H.anchor / H.img_w;                   // xs (image width)
     o.nbox[1] = H.cell_over_img * (cell_y + (float)h);        // yt
-    o.nbox[0] = H.cell_over_img * (cell_x + (float)w);        // xt
+    o.nbox[0] = H.cell_over_w * (cell_x + (float)w);          // xt
     return o;
 }
 
@@ -50,9 +50,9 @@ __device__ __forceinline__ void box_backward(const float* gn, const float* gb, c
     const float ryx = H.max_yx - H.min_yx, rhw = H.max_hw - H.min_hw;
     const float gq[4] = {
         (gb[1] + gn[1] * H.cell_over_img) * ryx,   // cell_y
-        (gb[0] + gn[0] * H.cell_over_img) * ryx,   // cell_x
+        (gb[0] + gn[0] * H.cell_over_w) * ryx,     // cell_x
         (gb[3] + gn[3] * H.anchor / H.img) * rhw,  // height
-        (gb[2] + gn[2] * H.anchor / H.img) * rhw,  // width
+        (gb[2] + gn[2] * H.anchor / H.img_w) * rhw,  // width
     };
 #pragma unroll
     for (int k = 0; k < 4; ++k) {

@@ -22,6 +22,8 @@ struct CellHyper {
     float count_prior_prob;   // sigmoid(log(v+1e-6)), models.py:186-188
     float range_yx, range_hw; // max - min of the two box ranges (fp32 differences, formed on the host: the chain kernels take them as scalar
                               // operands -- formed in the kernel the compiler hoists them into vector registers the forward chain does not have)
+    // the width axis: img and cell_over_img above are the height axis (image rows I); the same two for the image width Iw (= them when square)
+    float img_w, cell_over_w;
 };
 
 struct CellBufs {
@@ -30,7 +32,7 @@ struct CellBufs {
     // inputs
     const float* feat; int ld_feat;
     const float* edge;
-    const float *eps_box, *eps_attr, *eps_depth, *u_pres;   // NCHW maps [B,{4,A,1,1},G,G]
+    const float *eps_box, *eps_attr, *eps_depth, *u_pres;   // NCHW maps [B,{4,A,1,1},G,Gw]
     const float* gloss;                                     // device scalar dL/dloss
     // forward activations (row-major, row r = cprime*B + b)
     float *Xb, *Hb1, *Hb2, *Ob;
@@ -53,7 +55,7 @@ struct CellBufs {
     float* dfeat;
 };
 
-int cells_init_tables(int G, int LB, int* cell_h, int* cell_w, int* cidx, int* nbr, int* cons, int* diag_start, hipStream_t s);
+int cells_init_tables(int G, int Gw, int LB, int* cell_h, int* cell_w, int* cidx, int* nbr, int* cons, int* diag_start, hipStream_t s);
 int cells_ctx_gather(const CellLayout& L, const CellBufs& P, int r0, int R, hipStream_t s);
 int cells_box_sample(const CellLayout& L, const CellBufs& P, const CellHyper& H, int r0, int R, hipStream_t s);
 int cells_attr_sample(const CellLayout& L, const CellBufs& P, int r0, int R, hipStream_t s);
@@ -66,11 +68,14 @@ int cells_bwd_box(const CellLayout& L, const CellBufs& P, const CellHyper& H, in
 int cells_dfeat_edge(const CellLayout& L, const CellBufs& P, float* gedge, hipStream_t s);
 
 // stn.hip (rows r0 .. r0+R-1, row r reads image r % B), outgrad.hip, loss.hip
-int stn_glimpse_fwd(const float* x, const float* nbox, int B, float* out, int ld, int r0, int R, int C, int I, int P, int ac, int px16, hipStream_t s);
-int stn_glimpse_bwd(const float* x, const float* nbox, int B, const float* dgl, int ld, float* dnbox, int r0, int R, int C, int I, int P, int ac, int px16, hipStream_t s);
+// (images [B,C,Ih,Iw])
+int stn_glimpse_fwd(const float* x, const float* nbox, int B, float* out, int ld, int r0, int R, int C, int Ih, int Iw, int P, int ac, int px16,
+                    hipStream_t s);
+int stn_glimpse_bwd(const float* x, const float* nbox, int B, const float* dgl, int ld, float* dnbox, int r0, int R, int C, int Ih, int Iw, int P,
+                    int ac, int px16, hipStream_t s);
 int outgrad_recon_fold(const float* aux, const float* gloss, const float* grad_recon, const float* inv_den, float* aux_ext, float* one, int B,
-                       int C, int I, hipStream_t s);
-int outgrad_rows_fold(const int* cell_h, const int* cell_w, int B, int G, const float* g_z_where, const float* g_z_pres, float* g_nbox_r,
+                       int C, int Ih, int Iw, hipStream_t s);
+int outgrad_rows_fold(const int* cell_h, const int* cell_w, int B, int G, int Gw, const float* g_z_where, const float* g_z_pres, float* g_nbox_r,
                       float* g_pres_r, hipStream_t s);
 int loss_count_kl(const CellLayout& L, const CellBufs& P, float prior_prob, float* klp, hipStream_t s);
 int loss_gauss_kl_blocks(const CellLayout& L);

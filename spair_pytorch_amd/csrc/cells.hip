@@ -11,7 +11,7 @@ __global__ __launch_bounds__(128) void k_ctx_gather(CellLayout L, CellBufs P, in
     const int r = r0 + blockIdx.x;
     const int cp = r / L.B, b = r - cp * L.B;
     const int h = P.cell_h[cp], w = P.cell_w[cp];
-    const float* frow = P.feat + ((size_t)(b * L.G + h) * L.G + w) * P.ld_feat;
+    const float* frow = P.feat + ((size_t)(b * L.G + h) * L.Gw + w) * P.ld_feat;
     for (int col = threadIdx.x; col < L.F + L.CTX; col += blockDim.x) {
         float v;
         if (col < L.F) {
@@ -39,7 +39,7 @@ __global__ __launch_bounds__(128) void k_box_sample(CellLayout L, CellBufs P, Ce
     const int h = P.cell_h[cp], w = P.cell_w[cp];
     float eps[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) eps[k] = P.eps_box[(((size_t)b * 4 + k) * L.G + h) * L.G + w];
+    for (int k = 0; k < 4; ++k) eps[k] = P.eps_box[(((size_t)b * 4 + k) * L.G + h) * L.Gw + w];
     const BoxFwd o = box_forward(ob + L.ob_lat, eps, H, h, w);
     float* st = P.stat + (size_t)r * SP_LDSTAT;
 #pragma unroll
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(128) void k_box_sample(CellLayout L, CellBufs P, Ce
         P.Xz[(size_t)r * L.ld_x + L.x_box + k] = o.box[k];
         P.Xo[(size_t)r * L.ld_x + L.x_box + k] = o.box[k];
         P.nbox[(size_t)r * 4 + k] = o.nbox[k];
-        P.z_where[(((size_t)b * 4 + k) * L.G + h) * L.G + w] = o.nbox[k];
+        P.z_where[(((size_t)b * 4 + k) * L.G + h) * L.Gw + w] = o.nbox[k];
     }
 }
 
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(64) void k_attr_sample(CellLayout L, CellBufs P, in
     const float* oe = P.Oe + (size_t)r * L.ld_oe;
     for (int j = threadIdx.x; j < L.A; j += blockDim.x) {
         const float mean = oe[j];
-        const float eps = P.eps_attr[(((size_t)b * L.A + j) * L.G + h) * L.G + w];
+        const float eps = P.eps_attr[(((size_t)b * L.A + j) * L.G + h) * L.Gw + w];
         float std_, attr;
         attr_forward(mean, oe[L.A + j], eps, std_, attr);
         P.sd_attr[(size_t)r * L.ld_rec + j] = std_;
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(128) void k_depth_sample(CellLayout L, CellBufs P, 
     for (int i = threadIdx.x; i < L.NP; i += blockDim.x) P.Xo[(size_t)r * L.ld_x + L.x_pass + i] = oz[i];
     if (threadIdx.x != 0) return;
     const int h = P.cell_h[cp], w = P.cell_w[cp];
-    const float eps = P.eps_depth[((size_t)b * L.G + h) * L.G + w];
+    const float eps = P.eps_depth[((size_t)b * L.G + h) * L.Gw + w];
     float mean, std_, depth;
     depth_forward(oz[L.oz_lat], oz[L.oz_lat + 1], eps, H, mean, std_, depth);
     float* st = P.stat + (size_t)r * SP_LDSTAT;
@@ -104,10 +104,10 @@ __global__ __launch_bounds__(256) void k_pres_sample(CellLayout L, CellBufs P, C
     const int r = r0 + i;
     const int cp = r / L.B, b = r - cp * L.B;
     const int h = P.cell_h[cp], w = P.cell_w[cp];
-    const float u = P.u_pres[((size_t)b * L.G + h) * L.G + w];
+    const float u = P.u_pres[((size_t)b * L.G + h) * L.Gw + w];
     const float pres = pres_forward(P.Oo[(size_t)r * L.ld_oo], u, H);
     P.rec[(size_t)r * L.ld_rec + L.REC - 1] = pres;
-    P.z_pres[((size_t)b * L.G + h) * L.G + w] = pres;
+    P.z_pres[((size_t)b * L.G + h) * L.Gw + w] = pres;
 }
 
 // =============================================================================================
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(128) void k_bwd_depth(CellLayout L, CellBufs P, Cel
     const int h = P.cell_h[cp], w = P.cell_w[cp];
     const float ks = H.kl_scale * (*P.gloss);
     const float* st = P.stat + (size_t)r * SP_LDSTAT;
-    const float eps = P.eps_depth[((size_t)b * L.G + h) * L.G + w];
+    const float eps = P.eps_depth[((size_t)b * L.G + h) * L.Gw + w];
     const float zp = P.rec[(size_t)r * L.ld_rec + L.REC - 1];
     const float g_depth = P.grec[(size_t)r * L.ld_rec + 4 + L.A] + P.dXo[(size_t)r * L.ld_x + L.x_depth] + P.g_depth_r[r];
     depth_backward(g_depth, st[ST_MU_DEPTH], st[ST_SD_DEPTH], P.Oz[(size_t)r * L.ld_oz + L.oz_lat + 1], eps, zp, ks, H, doz[L.oz_lat],
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(64) void k_bwd_attr(CellLayout L, CellBufs P, CellH
     for (int j = threadIdx.x; j < L.A; j += blockDim.x) {
         const float g = P.grec[(size_t)r * L.ld_rec + 4 + j] + P.dXz[(size_t)r * L.ld_x + L.x_attr + j] +
                         P.dXo[(size_t)r * L.ld_x + L.x_attr + j] + P.g_attr_r[(size_t)r * L.ld_rec + j];
-        const float eps = P.eps_attr[(((size_t)b * L.A + j) * L.G + h) * L.G + w];
+        const float eps = P.eps_attr[(((size_t)b * L.A + j) * L.G + h) * L.Gw + w];
         attr_backward(g, P.Oe[(size_t)r * L.ld_oe + j], P.sd_attr[(size_t)r * L.ld_rec + j], P.Oe[(size_t)r * L.ld_oe + L.A + j], eps, zp, ks,
                       H, P.dOe[(size_t)r * L.ld_oe + j], P.dOe[(size_t)r * L.ld_oe + L.A + j]);
     }
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(128) void k_bwd_box(CellLayout L, CellBufs P, CellH
     }
     float eps[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) eps[k] = P.eps_box[(((size_t)b * 4 + k) * L.G + h) * L.G + w];
+    for (int k = 0; k < 4; ++k) eps[k] = P.eps_box[(((size_t)b * 4 + k) * L.G + h) * L.Gw + w];
     box_backward(gn, gb, st + ST_MU_BOX, st + ST_SD_BOX, eps, P.Ob + (size_t)r * L.ld_ob + L.ob_lat + 4, zp, ks, H, dob + L.ob_lat);
 }
 
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void k_dfeat_edge(CellLayout L, CellBufs P, in
             const float v = P.dXb[(size_t)r * L.ld_xb + c] + P.dXz[(size_t)r * L.ld_x + c] + P.dXo[(size_t)r * L.ld_x + c];
             if (s < 0) {
                 const int h = P.cell_h[cp], w = P.cell_w[cp];
-                P.dfeat[((size_t)(b * L.G + h) * L.G + w) * P.ld_feat + c] = v;
+                P.dfeat[((size_t)(b * L.G + h) * L.Gw + w) * P.ld_feat + c] = v;
             } else if (P.nbr[cp * L.NB + s] < 0) {
                 acc += v;
             }
@@ -234,15 +234,17 @@ __global__ __launch_bounds__(256) void k_dfeat_edge(CellLayout L, CellBufs P, in
 
 // ---- tables: wavefront order, neighbours, consumers -----------------------------------------
 // LB = N_LOOKBACK: cell (h, w) reads rows h-LB..h, columns w-LB..w+LB of the cells before it, so t = (LB+1) h + w is a dependency order
-// (its latest input, (h-1, w+LB), has t - 1); LB = 1 gives the 3G-2 anti-diagonals of UL, U, UR, L.
-__global__ __launch_bounds__(1024) void k_init_tables(int G, int LB, int* cell_h, int* cell_w, int* cidx, int* nbr, int* cons, int* diag_start) {
-    __shared__ int dstart[5 * 32 + 2];
-    const int S = LB + 1, T = S * (G - 1) + G, HW = G * G, NB = 2 * LB * S;
+// (its latest input, (h-1, w+LB), has t - 1); LB = 1 gives the 3G-2 anti-diagonals of UL, U, UR, L.  A G x Gw grid (G rows) has
+// (LB+1)(G-1) + Gw wavefronts.
+#define CELLS_MAX_T 2048
+__global__ __launch_bounds__(1024) void k_init_tables(int G, int Gw, int LB, int* cell_h, int* cell_w, int* cidx, int* nbr, int* cons, int* diag_start) {
+    __shared__ int dstart[CELLS_MAX_T + 2];
+    const int S = LB + 1, T = S * (G - 1) + Gw, HW = G * Gw, NB = 2 * LB * S;
     if (threadIdx.x == 0) {
         int c = 0;
         for (int t = 0; t < T; ++t) {
             dstart[t] = c;
-            const int hlo = max(0, (t - (G - 1) + S - 1) / S), hhi = min(G - 1, t / S);   // 0 <= t - S h < G
+            const int hlo = max(0, (t - (Gw - 1) + S - 1) / S), hhi = min(G - 1, t / S);   // 0 <= t - S h < Gw
             c += max(0, hhi - hlo + 1);
         }
         dstart[T] = c;
@@ -252,11 +254,11 @@ __global__ __launch_bounds__(1024) void k_init_tables(int G, int LB, int* cell_h
     // wavefront index of cell (h,w): cells of wavefront t = S h + w are ordered by ascending h
     auto cp_of = [&](int h, int w) {
         const int t = S * h + w;
-        const int hlo = max(0, (t - (G - 1) + S - 1) / S);
+        const int hlo = max(0, (t - (Gw - 1) + S - 1) / S);
         return dstart[t] + (h - hlo);
     };
     for (int k = threadIdx.x; k < HW; k += blockDim.x) {
-        const int h = k / G, w = k - h * G;
+        const int h = k / Gw, w = k - h * Gw;
         const int c = cp_of(h, w);
         cell_h[c] = h; cell_w[c] = w; cidx[k] = c;
         // slots in the reference's order (models.py:297-304): rows -LB..0, columns -LB..LB, without the current cell and its right side
@@ -265,17 +267,17 @@ __global__ __launch_bounds__(1024) void k_init_tables(int G, int LB, int* cell_h
         for (int dh = -LB; dh <= 0; ++dh)
             for (int dw = -LB; dw <= (dh ? LB : -1); ++dw, ++s) {
                 const int nh = h + dh, nw = w + dw;
-                nbr[c * NB + s] = (nh >= 0 && nh < G && nw >= 0 && nw < G) ? cp_of(nh, nw) : -1;
+                nbr[c * NB + s] = (nh >= 0 && nh < G && nw >= 0 && nw < Gw) ? cp_of(nh, nw) : -1;
                 const int qh = h - dh, qw = w - dw;   // the cell that sees (h,w) in slot s
-                cons[c * NB + s] = (qh >= 0 && qh < G && qw >= 0 && qw < G) ? cp_of(qh, qw) : -1;
+                cons[c * NB + s] = (qh >= 0 && qh < G && qw >= 0 && qw < Gw) ? cp_of(qh, qw) : -1;
             }
     }
 }
 
 // ---- host launchers -------------------------------------------------------------------------
-int cells_init_tables(int G, int LB, int* cell_h, int* cell_w, int* cidx, int* nbr, int* cons, int* diag_start, hipStream_t s) {
-    if (G > 32 || LB < 1 || LB > 3) return SPAIR_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(k_init_tables, dim3(1), dim3(1024), 0, s, G, LB, cell_h, cell_w, cidx, nbr, cons, diag_start);
+int cells_init_tables(int G, int Gw, int LB, int* cell_h, int* cell_w, int* cidx, int* nbr, int* cons, int* diag_start, hipStream_t s) {
+    if (G < 1 || Gw < 1 || G * Gw > 1024 || LB < 1 || LB > 3 || (LB + 1) * (G - 1) + Gw > CELLS_MAX_T) return SPAIR_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(k_init_tables, dim3(1), dim3(1024), 0, s, G, Gw, LB, cell_h, cell_w, cidx, nbr, cons, diag_start);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }

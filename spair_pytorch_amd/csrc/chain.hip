@@ -1705,8 +1705,8 @@ int chain_edge_reduce(const ChainArgs& a, hipStream_t s) {
     return SPAIR_OK;
 }
 
-int chain_fwd_supported(const SpairDims& d) {
-    return d.dtype == SPAIR_BF16 && d.lookback <= 1 && !d.obj_conv && d.F == F && d.A == A_ && d.NP == NP && d.P == 28 && d.C == 1 && d.G <= 32 &&
+int chain_fwd_supported(const SpairDims& d) {      // (square images only: the kernels index an I x I image and a G x G grid)
+    return spair_dims_square(spair_dims_norm(d)) && d.dtype == SPAIR_BF16 && d.lookback <= 1 && !d.obj_conv && d.F == F && d.A == A_ && d.NP == NP && d.P == 28 && d.C == 1 && d.G <= 32 &&
            (d.G + 1) / 2 <= MT && d.G >= 2;
 }
 

@@ -93,25 +93,28 @@ extern "C" int spair_prof_read(float* ms, int* counts, int nslots) {
 enum { PS_PREP = 0, PS_BACKBONE_FWD, PS_CELLS_FWD, PS_DECODER_FWD, PS_COUNT_KL, PS_RENDER_FWD, PS_LOSS, PS_RENDER_BWD, PS_DECODER_BWD,
        PS_CELLS_BWD, PS_CELLS_WGRAD, PS_BACKBONE_BWD, PS_CONV1_FWD, PS_DEC2_FWD, PS_STN_FWD, PS_ADAM, PS_DEC2_WGRAD, PS_DEC2_DGRAD };
 
+// d: normalised (spair_dims_norm) -- every entry point normalises the caller's struct once and hands that copy on
 static int validate(const SpairDims& d) {
     if (d.B <= 0 || d.I <= 0 || d.G <= 0 || d.P <= 0 || d.A <= 0 || d.F <= 0 || d.NP <= 0) return SPAIR_ERR_SHAPE;
+    if (d.Iw <= 0 || d.Gw <= 0 || d.pad_post_w < 0 || d.pad_post < 0 || d.pad_pre < 0) return SPAIR_ERR_SHAPE;
     if (d.C < 1 || d.C > 3) return SPAIR_ERR_UNSUPPORTED;  // colour channels: 1 (every tuned kernel) .. 3 (generic-channel renderer, render_c.hip)
     if (d.C != 1 && d.obj_conv) return SPAIR_ERR_UNSUPPORTED;      // colour images: the per-wavefront step (either dtype), MLP object nets
     if (d.n_conv < 1 || d.n_conv > SP_MAX_CONV) return SPAIR_ERR_SHAPE;
     if (d.dtype != SPAIR_F32 && d.dtype != SPAIR_BF16) return SPAIR_ERR_DTYPE;
     if ((d.F & 3) || (d.NP & 3)) return SPAIR_ERR_ALIGN;
-    int h = d.I + d.pad_pre + d.pad_post;
+    int h = d.I + d.pad_pre + d.pad_post, wd = d.Iw + d.pad_pre + d.pad_post_w;     // per axis: the padded frame down to the grid
     for (int i = 0; i < d.n_conv; ++i) {
         if (d.conv_k[i] < 1 || d.conv_s[i] < 1 || (d.conv_c[i] & 7)) return SPAIR_ERR_SHAPE;
         if (i > 0 && d.conv_k[i] > 1 && (d.conv_k[i] % d.conv_s[i] != 0 || d.conv_s[i] > 2)) return SPAIR_ERR_UNSUPPORTED;
         if (i > 0 && d.conv_k[i] == 1 && d.conv_s[i] != 1) return SPAIR_ERR_UNSUPPORTED;
         h = (h - d.conv_k[i]) / d.conv_s[i] + 1;
+        wd = (wd - d.conv_k[i]) / d.conv_s[i] + 1;
     }
-    if (h != d.G) return SPAIR_ERR_SHAPE;
-    if (d.G * d.G + 1 > 1025) return SPAIR_ERR_UNSUPPORTED;
+    if (h != d.G || wd != d.Gw) return SPAIR_ERR_SHAPE;
+    if ((long long)d.G * d.Gw + 1 > 1025) return SPAIR_ERR_UNSUPPORTED;     // the count-prior KL's one-workgroup limit (loss.hip)
     if (d.A + 5 > 64) return SPAIR_ERR_UNSUPPORTED;        // k_gauss_kl (loss.hip): one lane per latent element of a cell (A attributes + 4 box + 1 depth)
     if (d.lookback < 0 || d.lookback > 3) return SPAIR_ERR_UNSUPPORTED;
-    if (d.lookback > 1 && d.G > 32) return SPAIR_ERR_UNSUPPORTED;
+    if (d.lookback > 1 && std::max(d.G, d.Gw) > 32) return SPAIR_ERR_UNSUPPORTED;
     if (d.obj_conv) {   // convolutional object encoder / decoder variant: per-wavefront launches, the convolutions themselves in fp32 (objconv.hip)
         if (d.oc_n < 1 || d.oc_n > 4) return SPAIR_ERR_SHAPE;
         int hh = d.P, ci = d.C;
@@ -185,7 +188,7 @@ static Ws carve(const SpairDims& d, void* base) {
     const size_t es = d.dtype == SPAIR_BF16 ? 2 : 4;
     const size_t N = (size_t)L.N;
     w.cell_h = c.take<int>(L.HW); w.cell_w = c.take<int>(L.HW); w.cidx = c.take<int>(L.HW);
-    w.nbr = c.take<int>(L.NB * L.HW); w.cons = c.take<int>(L.NB * L.HW); w.diag_start = c.take<int>((L.LB + 2) * L.G + 2);
+    w.nbr = c.take<int>(L.NB * L.HW); w.cons = c.take<int>(L.NB * L.HW); w.diag_start = c.take<int>((L.LB + 1) * (L.G - 1) + L.Gw + 2);
     // prepared weights
     for (int i = 1; i < PL.n_conv; ++i) {
         const ConvSpec& cs = PL.conv[i];
@@ -221,22 +224,23 @@ static Ws carve(const SpairDims& d, void* base) {
     }
     w.dec_stream = d.dtype == SPAIR_BF16 ? c.take_bytes(dec_fused_stream_bytes(d.P * d.P * (d.C + 1))) : nullptr;
     // backbone
-    const int Ip = d.I + d.pad_pre + d.pad_post;
-    w.xpad = c.take<float>((size_t)d.B * Ip * Ip * d.C);
+    const int Ip = d.I + d.pad_pre + d.pad_post, Ipw = d.Iw + d.pad_pre + d.pad_post_w;
+    const bool square = spair_dims_square(d);
+    w.xpad = c.take<float>((size_t)d.B * Ip * Ipw * d.C);
     for (int i = 0; i < d.n_conv; ++i) {
         const ConvSpec& cs = PL.conv[i];
-        const size_t n = (size_t)d.B * cs.hout * cs.hout * cs.cout;
+        const size_t n = (size_t)d.B * cs.hout * cs.wout * cs.cout;
         w.act[i] = reinterpret_cast<float*>(c.take_bytes(n * es));      // NHWC, bf16 in bf16 mode
         w.dact[i] = reinterpret_cast<float*>(c.take_bytes(n * es));
     }
     {
         const ConvSpec& c0 = PL.conv[0];
-        w.act0_bits = misc_conv0_writes_mask(d.B, c0.hin, d.C, c0.k, c0.s, c0.cout, d.dtype == SPAIR_BF16)
+        w.act0_bits = square && misc_conv0_writes_mask(d.B, c0.hin, d.C, c0.k, c0.s, c0.cout, d.dtype == SPAIR_BF16)
                           ? c.take<unsigned char>((size_t)d.B * c0.hout * c0.hout * 16) : nullptr;
     }
     for (int i = 1; i < d.n_conv; ++i) {
         const ConvSpec& cs = PL.conv[i];
-        w.act_bits[i] = (d.dtype == SPAIR_BF16 && cs.k == 4 && cs.s == 2 && cs.cin == 128 && cs.cout == 128)
+        w.act_bits[i] = (square && d.dtype == SPAIR_BF16 && cs.k == 4 && cs.s == 2 && cs.cin == 128 && cs.cout == 128)
                             ? c.take<unsigned char>((size_t)d.B * cs.hout * cs.hout * 16) : nullptr;
     }
     w.ld_feat = round_up(d.F, 8);
@@ -274,8 +278,8 @@ static Ws carve(const SpairDims& d, void* base) {
     b.Za16 = w.Za16; b.dfeat16 = w.dfeat16;
     w.tn_part = reinterpret_cast<float*>(c.take_bytes((size_t)SPAIR_TN_PART_FLOATS * 4));
     w.tn_part2 = reinterpret_cast<float*>(c.take_bytes((size_t)SPAIR_TN_PART_FLOATS * 4));
-    w.aux = c.take<float>((size_t)d.B * d.C * d.I * d.I * 2);     // float2 per pixel and colour channel: (dBCE/dpre / D, pre)
-    w.bce_partial = c.take<float>(render_num_blocks(d.B, d.I));
+    w.aux = c.take<float>((size_t)d.B * d.C * d.I * d.Iw * 2);     // float2 per pixel and colour channel: (dBCE/dpre / D, pre)
+    w.bce_partial = c.take<float>(render_num_blocks(d.B, d.I, d.Iw));
     w.rrec = c.take_bytes(render_prep_bytes(d.B, L.HW));      // the renderer's per-object records (render3.hip)
     for (int i = 0; i < PL.oc_n; ++i) {
         const ConvSpec& e = PL.oc_enc[i];
@@ -299,8 +303,12 @@ static Ws carve(const SpairDims& d, void* base) {
     return w;
 }
 
-extern "C" int64_t spair_workspace_bytes(const SpairDims* d) {
-    if (!d || validate(*d) != SPAIR_OK) return -1;
+extern "C" int spair_abi_version(void) { return SPAIR_ABI_VERSION; }
+
+extern "C" int64_t spair_workspace_bytes(const SpairDims* d0) {
+    if (!d0) return -1;
+    const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
+    if (validate(*d) != SPAIR_OK) return -1;
     return (int64_t)carve(*d, nullptr).total;
 }
 
@@ -368,11 +376,11 @@ static std::vector<PInfo> param_infos(const SpairDims& d) {
     return v;
 }
 
-extern "C" int spair_param_count(const SpairDims* d) { return d ? (int)param_infos(*d).size() : -1; }
-extern "C" int64_t spair_param_total(const SpairDims* d) { return d ? make_param_layout(*d).total : -1; }
+extern "C" int spair_param_count(const SpairDims* d) { return d ? (int)param_infos(spair_dims_norm(*d)).size() : -1; }
+extern "C" int64_t spair_param_total(const SpairDims* d) { return d ? make_param_layout(spair_dims_norm(*d)).total : -1; }
 extern "C" int spair_param_info(const SpairDims* d, int idx, char* name, int name_cap, int64_t* offset, int64_t* shape4, int* ndim) {
     if (!d) return SPAIR_ERR_SHAPE;
-    const std::vector<PInfo> v = param_infos(*d);
+    const std::vector<PInfo> v = param_infos(spair_dims_norm(*d));
     if (idx < 0 || idx >= (int)v.size()) return SPAIR_ERR_SHAPE;
     snprintf(name, name_cap, "%s", v[idx].name);
     *offset = v[idx].off;
@@ -405,6 +413,7 @@ struct Ctx {
     ConvKernel conv_fwd[SP_MAX_CONV + 1], conv_dgrad[SP_MAX_CONV + 1];
     const unsigned char* dgrad_bits[SP_MAX_CONV + 1];      // a patch dgrad's gate: the sign bits the layer below left (null: its activation)
     StemWgrad stem_wgrad;
+    bool stem_unpadded;    // the stem reads the unpadded image itself (misc_conv0_reads_unpadded; square images)
     // the bf16 step's decoder backward
     bool dec_dgrad_fused;  // the three data gradients in one launch (dec_fused_bwd.hip; flags bit 6 turns it off)
     bool dec_wgrad_grouped;    // the two small weight gradients in one grouped launch
@@ -472,16 +481,16 @@ struct OnHelper {
 };
 
 static void fill_diag(Ctx& c) {
-    const int G = c.d.G;
+    const int G = c.d.G, Gw = c.d.Gw;    // grid rows, columns
     const int S = c.L.LB + 1;             // dependency wavefronts t = (N_LOOKBACK + 1) h + w (cells.hip, k_init_tables)
-    c.T = S * (G - 1) + G;
+    c.T = S * (G - 1) + Gw;
     c.dstart.assign(c.T + 1, 0);
     int n = 0;
     for (int t = 0; t < c.T; ++t) {
         c.dstart[t] = n;
         for (int h = 0; h < G; ++h) {
             const int w = t - S * h;
-            if (w >= 0 && w < G) ++n;
+            if (w >= 0 && w < Gw) ++n;
         }
     }
     c.dstart[c.T] = n;
@@ -666,7 +675,7 @@ static int prep_weights(Ctx& c, bool need_dgrad, int part) {
 // ---- backbone ------------------------------------------------------------------------------------------
 static ConvDesc fwd_desc(const ConvSpec& cs) {
     ConvDesc cd;
-    cd.Hin = cs.hin; cd.Win = cs.hin; cd.Cin = cs.cin; cd.Hout = cs.hout; cd.Wout = cs.hout; cd.kh = cs.k; cd.kw = cs.k;
+    cd.Hin = cs.hin; cd.Win = cs.win; cd.Cin = cs.cin; cd.Hout = cs.hout; cd.Wout = cs.wout; cd.kh = cs.k; cd.kw = cs.k;
     cd.sy = cs.s; cd.sx = cs.s; cd.dky = 1; cd.dkx = 1; cd.oy = 0; cd.ox = 0;
     return cd;
 }
@@ -675,10 +684,10 @@ static ConvDesc fwd_desc(const ConvSpec& cs) {
 // stored through the row map rm.  Returns the class's pixels per image (0: the class is empty).
 static int dgrad_class(const ConvSpec& cs, int py, int px, ConvDesc& dd, RowMap& rm) {
     const int T = cs.k / cs.s;
-    const int Hc = (cs.hin - py + cs.s - 1) / cs.s, Wc = (cs.hin - px + cs.s - 1) / cs.s;
-    dd.Hin = cs.hout; dd.Win = cs.hout; dd.Cin = cs.cout; dd.Hout = Hc; dd.Wout = Wc; dd.kh = T; dd.kw = T;
+    const int Hc = (cs.hin - py + cs.s - 1) / cs.s, Wc = (cs.win - px + cs.s - 1) / cs.s;
+    dd.Hin = cs.hout; dd.Win = cs.wout; dd.Cin = cs.cout; dd.Hout = Hc; dd.Wout = Wc; dd.kh = T; dd.kw = T;
     dd.sy = 1; dd.sx = 1; dd.dky = -1; dd.dkx = -1; dd.oy = 0; dd.ox = 0;
-    rm.Hout = Hc; rm.Wout = Wc; rm.Hc = cs.hin; rm.Wc = cs.hin; rm.osy = cs.s; rm.osx = cs.s; rm.ooy = py; rm.oox = px;
+    rm.Hout = Hc; rm.Wout = Wc; rm.Hc = cs.hin; rm.Wc = cs.win; rm.osy = cs.s; rm.osx = cs.s; rm.ooy = py; rm.oox = px;
     return Hc > 0 && Wc > 0 ? Hc * Wc : 0;
 }
 // All output-parity classes of layer i's data gradient in one nt16 launch (blockIdx.z = class; they have the same size): d out (A) is the
@@ -709,21 +718,26 @@ static bool decoder_small_wgrad_grouped_supported(const Ctx& c) {
 // ---- step plan -----------------------------------------------------------------------------------------
 // Which kernels the step runs (host arithmetic on c.d, c.L, c.PL and c.w only): make_ctx and the spair_step_plan diagnostics.  input_grad
 // (spair_backward_x): the image gradient reads d act0 from HBM, so the stem's weight gradient is not fused into conv_1's data gradient.
+// A rectangular image (Iw != I) refuses every square-only kernel here, in the plan, whatever their _supported predicates (most of which only
+// see I) say: the fused chain, the records / matrix-core / second-generation renderer (render_plan), the patch-resident strided convs, the
+// stem fused into conv_1's data gradient, its bf16 weight-gradient kernel and the stem variants that read the unpadded image.
 static void plan_step(Ctx& c, int flags, bool input_grad) {
     const SpairDims& d = c.d;
     const bool b16 = d.dtype == SPAIR_BF16;
-    c.use_chain = chain_fwd_supported(d) && !(flags & 1) && !d.obj_conv;
-    c.rg = {c.w.cb.nbox, c.w.cb.rec + (c.L.REC - 1), c.w.cb.rec + (c.L.REC - 2), c.L.ld_rec, d.B, c.L.HW, d.I, d.P, d.align_corners};
+    const bool square = d.Iw == d.I;
+    c.use_chain = square && chain_fwd_supported(d) && !(flags & 1) && !d.obj_conv;
+    c.rg = {c.w.cb.nbox, c.w.cb.rec + (c.L.REC - 1), c.w.cb.rec + (c.L.REC - 2), c.L.ld_rec, d.B, c.L.HW, d.I, d.P, d.align_corners, d.Iw};
     c.rp = render_plan(d, c.rg, c.w.ld_s, c.w.S, c.w.rrec, c.w.dLog);
     c.use_dec_fused = c.rp.s16 /* it writes fp16 sprites */ && !(flags & 16) && c.PL.lin[LIN_DEC0].out == SP_DEC_H1 && c.PL.lin[LIN_DEC1].out == SP_DEC_H2 &&
                       dec_fused_supported(d.A, d.P * d.P * (d.C + 1), c.L.ld_rec, c.L.N, c.w.ld_s);
     c.use_side = !(flags & 4);
     // backbone
     const ConvSpec& c0 = c.PL.conv[0];
-    const bool grey4 = c0.cin == 1 && c0.k == 4 && c0.cout == 128;
+    const bool grey4 = square && c0.cin == 1 && c0.k == 4 && c0.cout == 128;
     const bool fuse_stem = b16 && grey4 && !(flags & 8) && !input_grad;
-    const bool patch = b16 && !(flags & 32);
+    const bool patch = square && b16 && !(flags & 32);
     c.stem_wgrad = b16 && grey4 ? STEM_WGRAD16 : STEM_GENERIC;
+    c.stem_unpadded = square && misc_conv0_reads_unpadded(d.B, c0.hin, d.C, c0.k, c0.cout);
     const int n = c.PL.n_conv;      // the trailing run of 1x1 layers pointwise.hip fuses: 128 channels in, 128 out except the last, 2 to 4 layers
     c.pw0 = n;
     for (int i = n - 1; b16 && i >= 1; --i) {
@@ -745,7 +759,7 @@ static void plan_step(Ctx& c, int flags, bool input_grad) {
             if (i == 1 && fuse_stem &&
                 conv_s2k4_patch_dgrad16_stem_supported(d.B, cs.hout, cs.hin, cs.cin, cs.cout, cs.k, cs.s, c0.hin, c0.s, SPAIR_TN_PART_FLOATS))
                 c.stem_wgrad = STEM_PATCH;
-        } else if (b16 && cs.hin % cs.s == 0 && cs.s * cs.s <= 4) {
+        } else if (b16 && cs.hin % cs.s == 0 && cs.win % cs.s == 0 && cs.s * cs.s <= 4) {     // (every parity class the same size)
             c.conv_dgrad[i] = CONV_GEMM;
             if (i == 1 && fuse_stem && spair_nt16_stem_fusable(dgrad_classes16(c, 1), SPAIR_TN_PART_FLOATS)) c.stem_wgrad = STEM_GEMM;
         } else c.conv_dgrad[i] = CONV_PER_CLASS;
@@ -762,8 +776,9 @@ static void plan_step(Ctx& c, int flags, bool input_grad) {
 static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
                     const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace, void* stream, bool input_grad = false) {
     if (!d || !st || !params || !x || !workspace) return SPAIR_ERR_SHAPE;
-    TRY(validate(*d));
-    c.d = *d; c.st = *st;
+    c.d = spair_dims_norm(*d); c.st = *st;
+    TRY(validate(c.d));
+    d = &c.d;
     c.L = make_cell_layout(*d);
     c.PL = make_param_layout(*d);
     c.w = carve(*d, workspace);
@@ -771,6 +786,8 @@ static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const float
     CellHyper& H = c.H;
     H.wheel = st->wheel; H.kl_scale = st->kl_scale * d->vae_beta; H.img = (float)d->I; H.anchor = d->anchor;
     H.cell_over_img = (float)((double)d->cell_px / (double)d->I);
+    H.img_w = (float)d->Iw;
+    H.cell_over_w = (float)((double)d->cell_px / (double)d->Iw);
     H.max_yx = d->max_yx; H.min_yx = d->min_yx; H.max_hw = d->max_hw; H.min_hw = d->min_hw;
     H.range_yx = d->max_yx - d->min_yx; H.range_hw = d->max_hw - d->min_hw;
     for (int i = 0; i < 6; ++i) { H.prior_mean[i] = d->prior_mean[i]; H.prior_std[i] = d->prior_std[i]; }
@@ -788,10 +805,9 @@ static int backbone_stem_fwd(Ctx& c) {
     const int b16 = d.dtype == SPAIR_BF16;
     const ConvSpec& c0 = c.PL.conv[0];
     // the fast stem reads the unpadded image itself (spair_forward makes the padded copy on the helper stream, for the weight gradient)
-    if (!misc_conv0_reads_unpadded(d.B, c0.hin, d.C, c0.k, c0.cout))
-        TRY(misc_pad_input(c.x, c.w.xpad, d.B, d.C, d.I, d.pad_pre, d.I + d.pad_pre + d.pad_post, c.s));
+    if (!c.stem_unpadded) TRY(misc_pad_input(c.x, c.w.xpad, d.B, d.C, d.I, d.Iw, d.pad_pre, c0.hin, c0.win, c.s));
     return misc_conv0_fwd(c.x, c.w.xpad, c.params + c0.w, c.params + c0.b, c.w.act[0], d.B, d.I, d.pad_pre, c0.hin, d.C, c0.k, c0.s, c0.hout,
-                          c0.cout, b16, c.s, c.w.act0_bits);
+                          c0.cout, b16, c.s, c.w.act0_bits, c0.win, c0.wout, c.stem_unpadded);
 }
 static int backbone_fwd(Ctx& c) {
     const SpairDims& d = c.d;
@@ -800,7 +816,7 @@ static int backbone_fwd(Ctx& c) {
     for (int i = 1; i < c.PL.n_conv; ++i) {
         const ConvSpec& cs = c.PL.conv[i];
         const bool last = (i == c.PL.n_conv - 1);
-        const int M = d.B * cs.hout * cs.hout, K = cs.k * cs.k * cs.cin;
+        const int M = d.B * cs.hout * cs.wout, K = cs.k * cs.k * cs.cin;
         if (c.conv_fwd[i] == CONV_PW_STACK) {   // the trailing 1x1 layers (from pw0 on) run as one fused per-pixel MLP
             const void* W[4]; const float* bias[4]; void* Y[4]; int ldw[4], cout[4];
             const int Lp = c.PL.n_conv - pw0;
@@ -837,7 +853,7 @@ static int backbone_bwd16(Ctx& c, float* grads) {
     const SpairDims& d = c.d;
     const int last = c.PL.n_conv - 1, pw0 = c.pw0;
     const ConvSpec& c0 = c.PL.conv[0];
-    const int N = d.B * d.G * d.G;
+    const int N = d.B * d.G * d.Gw;
     if (!c.use_chain) TRY(spair_to_bf16(c.w.dfeat, c.w.ld_feat, c.w.dfeat16, c.w.ld_feat, N, c.w.ld_feat, c.s));   // the fused chain writes bf16 itself
     if (pw0 <= last) {   // data gradients of the trailing 1x1 layers: one fused kernel, top layer first
         const void* Wd[4]; const void* gate[4]; void* dX[4]; int ldw[4], cout[4];
@@ -868,7 +884,7 @@ static int backbone_bwd16(Ctx& c, float* grads) {
     }
     for (int i = pw0 - 1; i >= 1; --i) {      // (the layers below the 1x1 stack)
         const ConvSpec& cs = c.PL.conv[i];
-        const int M = d.B * cs.hout * cs.hout;
+        const int M = d.B * cs.hout * cs.wout;
         const void* dout = (i == last) ? c.w.dfeat16 : (const void*)c.w.dact[i];
         const int ldd = (i == last) ? c.w.ld_feat : cs.cout;
         const void* in = c.w.act[i - 1];
@@ -917,7 +933,7 @@ static int backbone_bwd16(Ctx& c, float* grads) {
     } else if (c.stem_wgrad == STEM_GENERIC) {
         const ConvDesc cd = fwd_desc(c0);
         const int K = c0.k * c0.k * c0.cin;
-        TRY(tn16(c, c.w.dact[0], c0.cout, c0.cout, c.w.xpad, 0, K, false, grads + c0.w, K, d.B * c0.hout * c0.hout, grads + c0.b, &cd, c0.cin,
+        TRY(tn16(c, c.w.dact[0], c0.cout, c0.cout, c.w.xpad, 0, K, false, grads + c0.w, K, d.B * c0.hout * c0.wout, grads + c0.b, &cd, c0.cin,
                  c0.k * c0.k));
     }
     return SPAIR_OK;
@@ -929,7 +945,7 @@ static int backbone_bwd(Ctx& c, float* grads) {
     const int last = c.PL.n_conv - 1;
     for (int i = last; i >= 1; --i) {
         const ConvSpec& cs = c.PL.conv[i];
-        const int M = d.B * cs.hout * cs.hout;
+        const int M = d.B * cs.hout * cs.wout;
         const float* dout = (i == last) ? c.w.dfeat : c.w.dact[i];
         const int ldd = (i == last) ? c.w.ld_feat : cs.cout;
         const float* in = c.w.act[i - 1];
@@ -955,7 +971,7 @@ static int backbone_bwd(Ctx& c, float* grads) {
     const ConvSpec& c0 = c.PL.conv[0];
     const ConvDesc cd = fwd_desc(c0);
     const int K = c0.k * c0.k * c0.cin;
-    return tn(c, c.w.dact[0], c0.cout, c0.cout, c.w.xpad, 0, K, grads + c0.w, K, d.B * c0.hout * c0.hout, grads + c0.b, &cd, c0.cin, c0.k * c0.k);
+    return tn(c, c.w.dact[0], c0.cout, c0.cout, c.w.xpad, 0, K, grads + c0.w, K, d.B * c0.hout * c0.wout, grads + c0.b, &cd, c0.cin, c0.k * c0.k);
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------
@@ -1112,7 +1128,8 @@ static int cells_fwd(Ctx& c) {
         }
         TRY(cells_box_sample(L, P, c.H, r0, R, c.s));
         // z_what
-        { ProfScope ps(PS_STN_FWD, c.s); TRY(stn_glimpse_fwd(c.x, P.nbox, L.B, P.glimpse, L.ld_gl, r0, R, c.d.C, c.d.I, c.d.P, c.d.align_corners, chain_image_fp16(c.d), c.s)); }
+        { ProfScope ps(PS_STN_FWD, c.s); TRY(stn_glimpse_fwd(c.x, P.nbox, L.B, P.glimpse, L.ld_gl, r0, R, c.d.C, c.d.I, c.d.Iw, c.d.P, c.d.align_corners, chain_image_fp16(c.d),
+                                                                c.s)); }
         if (PL.oc_n) TRY(oc_encoder_fwd(c, r0, R));
         else {
         TRY(fwd_lin(c, LIN_ENC0, P.glimpse, L.ld_gl, P.He1, SP_ENC_H1, r0, R, pr + PL.lin[LIN_ENC0].b, SP_ENC_H1, 1));
@@ -1145,6 +1162,7 @@ extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const 
                                  float* recon, float* z_where, float* z_pres, void* stream, float* inv_den) {
     Ctx c;
     TRY(make_ctx(c, d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, stream));
+    d = &c.d;      // normalised (spair_dims_norm)
     if (!loss_out || !recon || !z_where || !z_pres || !eps_box || !eps_attr || !eps_depth || !u_pres) return SPAIR_ERR_SHAPE;
     const CellLayout& L = c.L;
     CellBufs& P = c.w.cb;
@@ -1160,7 +1178,7 @@ extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const 
             ProfScope ps(PS_PREP, c.s);
             TRY(prep_weights(c, st->train != 0, 0));       // conv weights first: conv_1 waits for these only
             if (side && hipEventRecord(side->ev[3], side->s) != hipSuccess) return SPAIR_ERR_LAUNCH;
-            TRY(cells_init_tables(d->G, c.L.LB, c.w.cell_h, c.w.cell_w, c.w.cidx, c.w.nbr, c.w.cons, c.w.diag_start, c.s));
+            TRY(cells_init_tables(d->G, d->Gw, c.L.LB, c.w.cell_h, c.w.cell_w, c.w.cidx, c.w.nbr, c.w.cons, c.w.diag_start, c.s));
             if (st->draw_noise)
                 TRY(spair_noise_fill(d, st->noise_seed, const_cast<float*>(eps_box), const_cast<float*>(eps_attr), const_cast<float*>(eps_depth),
                                      const_cast<float*>(u_pres), c.s));
@@ -1169,8 +1187,7 @@ extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const 
         if (side && hipEventRecord(side->ev[4], side->s) != hipSuccess) return SPAIR_ERR_LAUNCH;
         // the padded copy is only read by the stem's weight gradient: it stays behind the event conv_1 waits on (the helper stream's
         // later joins order it before the backward)
-        if (misc_conv0_reads_unpadded(d->B, c.PL.conv[0].hin, d->C, c.PL.conv[0].k, c.PL.conv[0].cout))
-            TRY(misc_pad_input(x, c.w.xpad, d->B, d->C, d->I, d->pad_pre, d->I + d->pad_pre + d->pad_post, c.s));
+        if (c.stem_unpadded) TRY(misc_pad_input(x, c.w.xpad, d->B, d->C, d->I, d->Iw, d->pad_pre, c.PL.conv[0].hin, c.PL.conv[0].win, c.s));
     }
     const int ps_bb = prof_begin(PS_BACKBONE_FWD, c.s);
     TRY(backbone_stem_fwd(c));
@@ -1244,7 +1261,7 @@ extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const 
     }
     if (side && hipStreamWaitEvent(c.s, side->ev[1], 0) != hipSuccess) return SPAIR_ERR_LAUNCH;
     ProfScope psl(PS_LOSS, c.s);
-    TRY(loss_finalize(c.w.bce_partial, render_num_blocks(d->B, d->I), c.w.kl_partial, loss_gauss_kl_blocks(L), c.w.klp, d->B,
+    TRY(loss_finalize(c.w.bce_partial, render_num_blocks(d->B, d->I, d->Iw), c.w.kl_partial, loss_gauss_kl_blocks(L), c.w.klp, d->B,
                       st->kl_scale, d->vae_beta, loss_out,
                       c.use_chain && c.w.chain_sync ? c.w.chain_sync + CHAIN_SYNC_STICKY(d->B, chain_bands(*d)) : nullptr, st->status,
                       st->status_host, c.s));
@@ -1356,7 +1373,7 @@ static int decoder_small_wgrad_grouped(Ctx& c, float* grads, long long N) {
 // all-reduce on its own stream while the remaining backward kernels run.
 extern "C" int spair_grad_buckets(const SpairDims* d, int64_t* lo3, int64_t* hi3) {
     if (!d || !lo3 || !hi3) return SPAIR_ERR_SHAPE;
-    const ParamLayout P = make_param_layout(*d);
+    const ParamLayout P = make_param_layout(spair_dims_norm(*d));
     lo3[0] = P.lin[LIN_DEC0].w; hi3[0] = P.attn_gamma;        // decoder (first ready)
     lo3[1] = P.lin[LIN_BOX0].w; hi3[1] = P.lin[LIN_DEC0].w;   // box / encoder / z / obj nets
     lo3[2] = 0; hi3[2] = P.lin[LIN_BOX0].w;                   // edge element + backbone (last)
@@ -1404,13 +1421,15 @@ extern "C" int spair_backward_ev(const SpairDims* d, const SpairStep* st, const 
                               ev_backbone, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
-int input_grad_glimpse(const float* nbox, int B, int ncell, const float* dgl, int ld, float* out, int C, int I, int P, int ac, hipStream_t s);
-int input_grad_stem(const void* dact, int dact_bf16, const float* w, int B, int C, int I, int pre, int k, int s, int Hout, int Cout,
+int input_grad_glimpse(const float* nbox, int B, int ncell, const float* dgl, int ld, float* out, int C, int I, int Iw, int P, int ac, hipStream_t s);
+int input_grad_stem(const void* dact, int dact_bf16, const float* w, int B, int C, int I, int Iw, int pre, int k, int s, int Hout, int Wout, int Cout,
                     const float* add, const float* aux, const float* bce_g, float* grad_x, hipStream_t st);
 
-extern "C" int64_t spair_input_grad_scratch_bytes(const SpairDims* d) {
-    if (!d || validate(*d) != SPAIR_OK) return -1;
-    return ((int64_t)d->B * d->C * d->I * d->I * 4 + 255) & ~(int64_t)255;      // dx_gl [B][C][I][I] fp32
+extern "C" int64_t spair_input_grad_scratch_bytes(const SpairDims* d0) {
+    if (!d0) return -1;
+    const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
+    if (validate(*d) != SPAIR_OK) return -1;
+    return ((int64_t)d->B * d->C * d->I * d->Iw * 4 + 255) & ~(int64_t)255;      // dx_gl [B][C][I][Iw] fp32
 }
 
 // grad_x == nullptr: exactly spair_backward_out.  Otherwise, once the parameter gradients are complete (after ev_backbone), the image
@@ -1422,6 +1441,7 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
                          float* aux_scratch, float* grad_x, int bce_target, float* x_scratch) {
     Ctx c;
     TRY(make_ctx(c, d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, stream, grad_x != nullptr));
+    d = &c.d;      // normalised (spair_dims_norm)
     if (!grad_loss || !grads) return SPAIR_ERR_SHAPE;
     if (grad_recon && (!inv_den || !aux_scratch)) return SPAIR_ERR_SHAPE;
     if (grad_x && (!x_scratch || c.PL.n_conv < 2)) return grad_x && !x_scratch ? SPAIR_ERR_SHAPE : SPAIR_ERR_UNSUPPORTED;
@@ -1439,8 +1459,8 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
     const float* r_aux = c.w.aux;
     const float* r_gloss = grad_loss;
     if (grad_recon) {
-        const size_t n2 = (size_t)d->B * d->C * d->I * d->I * 2;
-        TRY(outgrad_recon_fold(c.w.aux, grad_loss, grad_recon, inv_den, aux_scratch, aux_scratch + n2, d->B, d->C, d->I, c.s));
+        const size_t n2 = (size_t)d->B * d->C * d->I * d->Iw * 2;
+        TRY(outgrad_recon_fold(c.w.aux, grad_loss, grad_recon, inv_den, aux_scratch, aux_scratch + n2, d->B, d->C, d->I, d->Iw, c.s));
         r_aux = aux_scratch;
         r_gloss = aux_scratch + n2;
     }
@@ -1456,7 +1476,7 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
         else TRY(render_bwd_c(c.rg, c.w.S, c.w.ld_s, d->C, r_aux, r_gloss, c.w.dLog, P.g_nbox_r, P.g_pres_r, P.g_depth_r, c.w.ld_s, so, sa, c.s));
     }
     // adjoints of the z_where / z_pres outputs: added to the rows the renderer just wrote, before the per-cell backward reads them
-    TRY(outgrad_rows_fold(P.cell_h, P.cell_w, d->B, d->G, grad_z_where, grad_z_pres, P.g_nbox_r, P.g_pres_r, c.s));
+    TRY(outgrad_rows_fold(P.cell_h, P.cell_w, d->B, d->G, d->Gw, grad_z_where, grad_z_pres, P.g_nbox_r, P.g_pres_r, c.s));
     SideStream* side = nullptr;
     if (c.use_side) TRY(side_stream(side));
     std::unique_lock<std::mutex> enq_lock;
@@ -1533,7 +1553,8 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
         TRY(bwd_lin(c, LIN_ENC1, SP_ENC_H2, P.dHe2, SP_ENC_H2, P.dHe1, SP_ENC_H1, r0, R, P.He1, SP_ENC_H1));
         TRY(bwd_lin(c, LIN_ENC0, SP_ENC_H1, P.dHe1, SP_ENC_H1, P.dGl, L.ld_gl, r0, R, nullptr, 0));
         }
-        TRY(stn_glimpse_bwd(x, P.nbox, L.B, P.dGl, L.ld_gl, P.g_nbox_stn, r0, R, d->C, d->I, d->P, d->align_corners, chain_image_fp16(*d), c.s));
+        TRY(stn_glimpse_bwd(x, P.nbox, L.B, P.dGl, L.ld_gl, P.g_nbox_stn, r0, R, d->C, d->I, d->Iw, d->P, d->align_corners, chain_image_fp16(*d),
+                            c.s));
         TRY(cells_bwd_box(L, P, c.H, r0, R, c.s));
         TRY(bwd_lin(c, LIN_BOXH1, L.NP + 8, P.dOb, L.ld_ob, P.dHb2, SP_LDH, r0, R, P.Hb2, SP_LDH));
         TRY(bwd_lin(c, LIN_BOX1, SP_H, P.dHb2, SP_LDH, P.dHb1, SP_LDH, r0, R, P.Hb1, SP_LDH));
@@ -1583,9 +1604,10 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
             const int K = round_up(e0.out, 8);
             TRY(nt16(c, P.dHe1, SP_ENC_H1, c.w.lin_wt[LIN_ENC0], K, P.dGl, L.ld_gl, 0, N, e0.in, K, nullptr, nullptr, 0, 0));
         }
-        TRY(input_grad_glimpse(P.nbox, d->B, d->G * d->G, P.dGl, L.ld_gl, x_scratch, d->C, d->I, d->P, d->align_corners, c.s));
+        TRY(input_grad_glimpse(P.nbox, d->B, d->G * d->Gw, P.dGl, L.ld_gl, x_scratch, d->C, d->I, d->Iw, d->P, d->align_corners, c.s));
         const ConvSpec& c0 = PL.conv[0];
-        TRY(input_grad_stem(c.w.dact[0], b16, params + c0.w, d->B, d->C, d->I, d->pad_pre, c0.k, c0.s, c0.hout, c0.cout, x_scratch, c.w.aux,
+        TRY(input_grad_stem(c.w.dact[0], b16, params + c0.w, d->B, d->C, d->I, d->Iw, d->pad_pre, c0.k, c0.s, c0.hout, c0.wout, c0.cout, x_scratch,
+                            c.w.aux,
                             bce_target ? grad_loss : nullptr, grad_x, c.s));
     }
     return SPAIR_OK;
@@ -1611,8 +1633,9 @@ extern "C" int spair_backward_x(const SpairDims* d, const SpairStep* st, const f
 }
 
 // diagnostic: copy the forward chain kernel's stage stamps (SpairStep.flags bit 1) into a caller buffer of n uint64
-extern "C" int spair_chain_stamps(const SpairDims* d, const void* workspace, unsigned long long* out, int n, void* stream) {
-    if (!d || !workspace || !out || n > 4096) return SPAIR_ERR_SHAPE;
+extern "C" int spair_chain_stamps(const SpairDims* d0, const void* workspace, unsigned long long* out, int n, void* stream) {
+    if (!d0 || !workspace || !out || n > 4096) return SPAIR_ERR_SHAPE;
+    const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
     TRY(validate(*d));
     const Ws w = carve(*d, const_cast<void*>(workspace));
     if (hipMemcpyAsync(out, w.stamps, sizeof(unsigned long long) * n, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return SPAIR_ERR_LAUNCH;
@@ -1624,8 +1647,9 @@ static_assert(SPAIR_RENDER_MMA == RENDER_MMA && SPAIR_RENDER_GEN2 == RENDER_GEN2
 static_assert(SPAIR_STEP_PLAN_INTS == 14 + 3 * SP_MAX_CONV, "include/spair_hip.h lays out spair_step_plan_n");
 // diagnostic: the kernel plan make_ctx computes for these dims, workspace, SpairStep.flags and input gradient (host only: nothing launched,
 // nothing read)
-extern "C" int spair_step_plan_n(const SpairDims* d, const void* workspace, int flags, int input_grad, int* out, int n) {
-    if (!d || !workspace || !out) return SPAIR_ERR_SHAPE;
+extern "C" int spair_step_plan_n(const SpairDims* d0, const void* workspace, int flags, int input_grad, int* out, int n) {
+    if (!d0 || !workspace || !out) return SPAIR_ERR_SHAPE;
+    const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
     TRY(validate(*d));
     Ctx c;
     c.d = *d; c.L = make_cell_layout(*d); c.PL = make_param_layout(*d); c.w = carve(*d, const_cast<void*>(workspace));
@@ -1646,16 +1670,18 @@ extern "C" int spair_step_plan(const SpairDims* d, const void* workspace, int fl
 // band split of the fused chain kernels: 1 if a wait for the neighbouring band ever timed out in a launch on this workspace (STICKY: no
 // launch clears it; the step's loss and edge-element gradient are NaN from then on -- never seen, the test suite asserts 0), else 0; -1 where
 // the chain runs unsplit.  Copies one int to `out` (device).
-extern "C" int spair_chain_sync_status(const SpairDims* d, const void* workspace, int* out, void* stream) {
-    if (!d || !workspace || !out) return SPAIR_ERR_SHAPE;
+extern "C" int spair_chain_sync_status(const SpairDims* d0, const void* workspace, int* out, void* stream) {
+    if (!d0 || !workspace || !out) return SPAIR_ERR_SHAPE;
+    const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
     TRY(validate(*d));
     const Ws w = carve(*d, const_cast<void*>(workspace));
     if (!w.chain_sync) return hipMemsetAsync(out, 0xff, sizeof(int), (hipStream_t)stream) == hipSuccess ? SPAIR_OK : SPAIR_ERR_LAUNCH;
     return hipMemcpyAsync(out, w.chain_sync + CHAIN_SYNC_STICKY(d->B, chain_bands(*d)), sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess ? SPAIR_OK : SPAIR_ERR_LAUNCH;
 }
 // number of wavefronts the stamping workgroup (sample 0, top band) walks: 3G-2 unsplit, its band's share otherwise
-extern "C" int spair_chain_stamp_wavefronts(const SpairDims* d) {
-    if (!d) return SPAIR_ERR_SHAPE;
+extern "C" int spair_chain_stamp_wavefronts(const SpairDims* d0) {
+    if (!d0) return SPAIR_ERR_SHAPE;
+    const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
     const int nb = chain_fwd_supported(*d) ? chain_bands(*d) : 1;
     const int hb = (d->G + nb - 1) / nb;
     return 2 * (hb - 1) + d->G;
@@ -1670,8 +1696,9 @@ extern "C" int spair_chain_stamp_layout(int* fwd_per_wavefront, int* fwd_glimpse
 }
 
 // which: 0 z_attr, 1 z_depth, 2..7 mean of cy,cx,height,width,attr,depth, 8..13 sigma, 14 count-prior p_z
-extern "C" int spair_export_map(const SpairDims* d, const void* workspace, int which, float* out, void* stream) {
-    if (!d || !workspace || !out) return SPAIR_ERR_SHAPE;
+extern "C" int spair_export_map(const SpairDims* d0, const void* workspace, int which, float* out, void* stream) {
+    if (!d0 || !workspace || !out) return SPAIR_ERR_SHAPE;
+    const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
     TRY(validate(*d));
     const CellLayout L = make_cell_layout(*d);
     const Ws w = carve(*d, const_cast<void*>(workspace));
@@ -1694,8 +1721,8 @@ extern "C" int spair_export_map(const SpairDims* d, const void* workspace, int w
         else if (k == 1) { src = P.dOe; ld = L.ld_oe; col0 = 0; ch = 2 * L.A; }
         else if (k == 2) { src = P.dOz; ld = L.ld_oz; col0 = L.oz_lat; ch = 2; }
         else { src = P.dOo; ld = L.ld_oo; col0 = 0; ch = 1; }
-        if (which >= 200) return misc_export16(src, ld, col0, ch, w.cell_h, w.cell_w, d->B, d->G, out, s);
+        if (which >= 200) return misc_export16(src, ld, col0, ch, w.cell_h, w.cell_w, d->B, d->G, d->Gw, out, s);
     }
     else return SPAIR_ERR_SHAPE;
-    return misc_export(src, ld, col0, ch, w.cell_h, w.cell_w, d->B, d->G, out, s);
+    return misc_export(src, ld, col0, ch, w.cell_h, w.cell_w, d->B, d->G, d->Gw, out, s);
 }

@@ -14,10 +14,21 @@
 #define SP_DEC_H2 256
 #define SP_MAX_CONV 8
 
+// SpairDims with the rectangular-image fields made explicit (Iw, Gw, pad_post_w: 0 = the square value).  Every C entry point applies it once
+// to the caller's struct; everything below it reads Iw / Gw / pad_post_w as they are.
+static inline SpairDims spair_dims_norm(const SpairDims& d) {
+    SpairDims n = d;
+    if (n.Iw == 0) n.Iw = n.I;
+    if (n.Gw == 0) n.Gw = n.G;
+    if (n.pad_post_w == 0) n.pad_post_w = n.pad_post;
+    return n;
+}
+static inline bool spair_dims_square(const SpairDims& d) { return d.Iw == d.I && d.Gw == d.G && d.pad_post_w == d.pad_post; }
+
 // Row r = cprime * B + b, where cprime enumerates cells in dependency-wavefront order
-// (t = 2h + w ascending, then h ascending): every diagonal is a contiguous row range.
+// (t = (LB+1)h + w ascending, then h ascending): every diagonal is a contiguous row range.
 struct CellLayout {
-    int B, G, HW, N;            // N = B*HW
+    int B, G, HW, N;            // G: grid rows (Gh), HW = G*Gw, N = B*HW
     int F, A, NP, REC;          // backbone features, attrs, passthrough, record width (4+A+2)
     int LB, NB;                 // N_LOOKBACK and its 2*LB*(LB+1) context neighbours
     int CTX;                    // NB*REC
@@ -31,11 +42,12 @@ struct CellLayout {
     int ld_rec;                 // record [box4 | attr A | depth | pres]
     int glimpse;                // C*P*P
     int ld_gl;
+    int Gw;                     // grid columns
 };
 
 static inline CellLayout make_cell_layout(const SpairDims& d) {
     CellLayout L;
-    L.B = d.B; L.G = d.G; L.HW = d.G * d.G; L.N = d.B * L.HW;
+    L.B = d.B; L.G = d.G; L.Gw = d.Gw; L.HW = d.G * d.Gw; L.N = d.B * L.HW;
     L.F = d.F; L.A = d.A; L.NP = d.NP; L.REC = 4 + d.A + 2;
     L.LB = d.lookback > 0 ? d.lookback : 1; L.NB = 2 * L.LB * (L.LB + 1); L.CTX = L.NB * L.REC;
     L.x_ctx = L.F; L.x_pass = L.F + L.CTX; L.x_box = L.x_pass + L.NP; L.x_attr = L.x_box + 4;
@@ -63,7 +75,8 @@ enum LinId {
 };
 
 struct LinSpec { int in, out; int64_t w, b; };
-struct ConvSpec { int cin, cout, k, s; int hin, hout; int64_t w, b; };  // square images
+struct ConvSpec { int cin, cout, k, s; int hin, hout; int64_t w, b; int win, wout; };  // square kernels; win / wout: the width axis (= hin / hout for
+                                                                            // the object nets' square glimpses)
 
 struct ParamLayout {
     int64_t edge;
@@ -90,18 +103,19 @@ static inline ParamLayout make_param_layout(const SpairDims& d) {
     const CellLayout L = make_cell_layout(d);
     P.edge = pl_take(cur, L.REC);
     P.n_conv = d.n_conv + 1;
-    int cin = d.C, h = d.I + d.pad_pre + d.pad_post;
+    int cin = d.C, h = d.I + d.pad_pre + d.pad_post, wd = d.Iw + d.pad_pre + d.pad_post_w;
     for (int i = 0; i < d.n_conv; ++i) {
         ConvSpec& c = P.conv[i];
         c.cin = cin; c.cout = d.conv_c[i]; c.k = d.conv_k[i]; c.s = d.conv_s[i];
         c.hin = h; c.hout = (h - c.k) / c.s + 1;
+        c.win = wd; c.wout = (wd - c.k) / c.s + 1;
         c.w = pl_take(cur, (int64_t)c.cout * cin * c.k * c.k);
         c.b = pl_take(cur, c.cout);
-        cin = c.cout; h = c.hout;
+        cin = c.cout; h = c.hout; wd = c.wout;
     }
     {
         ConvSpec& c = P.conv[d.n_conv];
-        c.cin = cin; c.cout = d.F; c.k = 1; c.s = 1; c.hin = h; c.hout = h;
+        c.cin = cin; c.cout = d.F; c.k = 1; c.s = 1; c.hin = h; c.hout = h; c.win = wd; c.wout = wd;
         c.w = pl_take(cur, (int64_t)c.cout * cin);
         c.b = pl_take(cur, c.cout);
     }
@@ -118,7 +132,7 @@ static inline ParamLayout make_param_layout(const SpairDims& d) {
         for (int i = 0; i < d.oc_n; ++i) {
             ConvSpec& c = P.oc_enc[i];
             c.cin = ci; c.cout = d.oc_c[i]; c.k = d.oc_k[i]; c.s = d.oc_s[i];
-            c.hin = hh; c.hout = (hh - c.k) / c.s + 1;
+            c.hin = hh; c.hout = (hh - c.k) / c.s + 1; c.win = c.hin; c.wout = c.hout;
             c.w = pl_take(cur, (int64_t)c.cout * ci * c.k * c.k);
             c.b = pl_take(cur, c.cout);
             ci = c.cout; hh = c.hout;
@@ -137,7 +151,7 @@ static inline ParamLayout make_param_layout(const SpairDims& d) {
             const ConvSpec& e = P.oc_enc[d.oc_n - 1 - i];
             ConvSpec& c = P.oc_dec[i];
             c.cin = e.cout; c.cout = (d.oc_n - 1 - i == 0) ? d.C + 1 : e.cin; c.k = e.k; c.s = e.s;
-            c.hin = e.hout; c.hout = e.hin;
+            c.hin = e.hout; c.hout = e.hin; c.win = c.hin; c.wout = c.hout;
             c.w = pl_take(cur, (int64_t)c.cin * c.cout * c.k * c.k);
             c.b = pl_take(cur, c.cout);
         }

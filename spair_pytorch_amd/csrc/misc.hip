@@ -107,7 +107,8 @@ __global__ __launch_bounds__(256) void k_noise(uint64_t seed, float* eps_box, lo
 
 extern "C" int spair_noise_fill(const SpairDims* d, uint64_t seed, float* eps_box, float* eps_attr, float* eps_depth,
                                 float* u_pres, void* stream) {
-    const long long cells = (long long)d->B * d->G * d->G;
+    if (!d) return SPAIR_ERR_SHAPE;
+    const long long cells = (long long)d->B * d->G * (d->Gw ? d->Gw : d->G);      // (a C entry point: Gw = 0 is the square grid)
     const long long total = cells * (4 + d->A + 2);
     hipLaunchKernelGGL(k_noise, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed, eps_box, cells * 4,
                        eps_attr, cells * d->A, eps_depth, cells, u_pres, cells);
@@ -115,23 +116,23 @@ extern "C" int spair_noise_fill(const SpairDims* d, uint64_t seed, float* eps_bo
     return SPAIR_OK;
 }
 
-// ---- input: NCHW [B,C,I,I] -> zero-padded NHWC [B,Ip,Ip,C] (modules.py:105,108) ----------------
-__global__ __launch_bounds__(256) void k_pad_input(const float* __restrict__ x, float* __restrict__ xp, int B, int C, int I, int pre,
-                                                   int Ip) {
+// ---- input: NCHW [B,C,I,Iw] -> zero-padded NHWC [B,Ip,Ipw,C] (modules.py:105,108): pre pixels before either axis -------------
+__global__ __launch_bounds__(256) void k_pad_input(const float* __restrict__ x, float* __restrict__ xp, int B, int C, int I, int Iw, int pre,
+                                                   int Ip, int Ipw) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long total = (long long)B * Ip * Ip * C;
+    const long long total = (long long)B * Ip * Ipw * C;
     if (idx >= total) return;
     const int c = (int)(idx % C);
     long long t = idx / C;
-    const int px = (int)(t % Ip); t /= Ip;
+    const int px = (int)(t % Ipw); t /= Ipw;
     const int py = (int)(t % Ip);
     const int b = (int)(t / Ip);
     const int sx = px - pre, sy = py - pre;
-    xp[idx] = (sx >= 0 && sx < I && sy >= 0 && sy < I) ? x[(((size_t)b * C + c) * I + sy) * I + sx] : 0.f;
+    xp[idx] = (sx >= 0 && sx < Iw && sy >= 0 && sy < I) ? x[(((size_t)b * C + c) * I + sy) * Iw + sx] : 0.f;
 }
-int misc_pad_input(const float* x, float* xp, int B, int C, int I, int pre, int Ip, hipStream_t s) {
-    const long long total = (long long)B * Ip * Ip * C;
-    hipLaunchKernelGGL(k_pad_input, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, xp, B, C, I, pre, Ip);
+int misc_pad_input(const float* x, float* xp, int B, int C, int I, int Iw, int pre, int Ip, int Ipw, hipStream_t s) {
+    const long long total = (long long)B * Ip * Ipw * C;
+    hipLaunchKernelGGL(k_pad_input, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, xp, B, C, I, Iw, pre, Ip, Ipw);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
@@ -204,37 +205,37 @@ int misc_prep(const PrepTable& T, hipStream_t s) {
 
 // ---- per-row quantity -> NCHW map -----------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_export(const float* __restrict__ src, int ld, int col0, int ch, const int* __restrict__ cell_h,
-                                                const int* __restrict__ cell_w, int B, int G, float* __restrict__ out) {
+                                                const int* __restrict__ cell_w, int B, int G, int Gw, float* __restrict__ out) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long total = (long long)B * G * G * ch;
+    const long long total = (long long)B * G * Gw * ch;
     if (idx >= total) return;
     const int c = (int)(idx % ch);
     const long long r = idx / ch;
     const int cp = (int)(r / B), b = (int)(r - (long long)cp * B);
-    out[(((size_t)b * ch + c) * G + cell_h[cp]) * G + cell_w[cp]] = src[r * ld + col0 + c];
+    out[(((size_t)b * ch + c) * G + cell_h[cp]) * Gw + cell_w[cp]] = src[r * ld + col0 + c];
 }
 // the same from a row buffer stored as bf16 (the fused chain's gradient rows: same leading dimension in ELEMENTS)
 __global__ __launch_bounds__(256) void k_export16(const __bf16* __restrict__ src, int ld, int col0, int ch, const int* __restrict__ cell_h,
-                                                  const int* __restrict__ cell_w, int B, int G, float* __restrict__ out) {
+                                                  const int* __restrict__ cell_w, int B, int G, int Gw, float* __restrict__ out) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long long total = (long long)B * G * G * ch;
+    const long long total = (long long)B * G * Gw * ch;
     if (idx >= total) return;
     const int c = (int)(idx % ch);
     const long long r = idx / ch;
     const int cp = (int)(r / B), b = (int)(r - (long long)cp * B);
-    out[(((size_t)b * ch + c) * G + cell_h[cp]) * G + cell_w[cp]] = (float)src[r * ld + col0 + c];
+    out[(((size_t)b * ch + c) * G + cell_h[cp]) * Gw + cell_w[cp]] = (float)src[r * ld + col0 + c];
 }
-int misc_export16(const void* src, int ld, int col0, int ch, const int* cell_h, const int* cell_w, int B, int G, float* out, hipStream_t s) {
-    const long long total = (long long)B * G * G * ch;
+int misc_export16(const void* src, int ld, int col0, int ch, const int* cell_h, const int* cell_w, int B, int G, int Gw, float* out, hipStream_t s) {
+    const long long total = (long long)B * G * Gw * ch;
     hipLaunchKernelGGL(k_export16, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const __bf16*>(src), ld, col0, ch,
-                       cell_h, cell_w, B, G, out);
+                       cell_h, cell_w, B, G, Gw, out);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
-int misc_export(const float* src, int ld, int col0, int ch, const int* cell_h, const int* cell_w, int B, int G, float* out,
+int misc_export(const float* src, int ld, int col0, int ch, const int* cell_h, const int* cell_w, int B, int G, int Gw, float* out,
                 hipStream_t s) {
-    const long long total = (long long)B * G * G * ch;
-    hipLaunchKernelGGL(k_export, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, ld, col0, ch, cell_h, cell_w, B, G, out);
+    const long long total = (long long)B * G * Gw * ch;
+    hipLaunchKernelGGL(k_export, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, ld, col0, ch, cell_h, cell_w, B, G, Gw, out);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
@@ -242,7 +243,8 @@ int misc_export(const float* src, int ld, int col0, int ch, const int* cell_h, c
 // ---- backbone layer 0 (Cin = C, tiny K = k*k*C): direct kernels -------------------------------------
 // forward: out[m][co] = relu(bias[co] + sum_k w[co][k] * patch(m)[k]); weights in LDS; thread = (pixel, 4 channels)
 __global__ __launch_bounds__(256) void k_conv0_fwd(const float* __restrict__ xp, const float* __restrict__ w, const float* __restrict__ bias,
-                                                   float* __restrict__ out, int B, int Hin, int C, int k, int s, int Hout, int Cout, int out_bf16) {
+                                                   float* __restrict__ out, int B, int Hin, int Win, int C, int k, int s, int Hout, int Wout, int Cout,
+                                                   int out_bf16) {
     extern __shared__ float wsh[];   // [K0][Cout] transposed for conflict-free float4 reads
     const int K0 = k * k * C;
     for (int i = threadIdx.x; i < K0 * Cout; i += blockDim.x) {
@@ -252,14 +254,14 @@ __global__ __launch_bounds__(256) void k_conv0_fwd(const float* __restrict__ xp,
     }
     __syncthreads();
     const int q = Cout / 4;
-    const long long total = (long long)B * Hout * Hout * q;
+    const long long total = (long long)B * Hout * Wout * q;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
         const int cq = (int)(idx % q);
         const long long m = idx / q;
-        const int ox = (int)(m % Hout), oy = (int)((m / Hout) % Hout), b = (int)(m / ((long long)Hout * Hout));
+        const int ox = (int)(m % Wout), oy = (int)((m / Wout) % Hout), b = (int)(m / ((long long)Hout * Wout));
         float4 acc = *reinterpret_cast<const float4*>(bias + cq * 4);
         for (int ky = 0; ky < k; ++ky) {
-            const float* row = xp + (((size_t)b * Hin + oy * s + ky) * Hin + ox * s) * C;
+            const float* row = xp + (((size_t)b * Hin + oy * s + ky) * Win + ox * s) * C;
             for (int t = 0; t < k * C; ++t) {
                 const float xv = row[t];
                 const float4 wv = *reinterpret_cast<const float4*>(&wsh[((ky * k * C) + t) * Cout + cq * 4]);
@@ -478,9 +480,10 @@ bool misc_conv0_writes_mask(int B, int Hin, int C, int k, int s, int Cout, int o
     return misc_conv0_reads_unpadded(B, Hin, C, k, Cout) && out_bf16 && Cout == 128 && s == 2 && (Hin & 1) == 0;
 }
 int misc_conv0_fwd(const float* x, const float* xp, const float* w, const float* bias, float* out, int B, int I, int pre, int Hin, int C, int k,
-                   int s, int Hout, int Cout, int out_bf16, hipStream_t st, unsigned char* mask) {
+                   int s, int Hout, int Cout, int out_bf16, hipStream_t st, unsigned char* mask, int Win, int Wout, bool unpadded) {
     if (Cout % 4) return SPAIR_ERR_ALIGN;
-    if (misc_conv0_reads_unpadded(B, Hin, C, k, Cout)) {
+    if (Win == 0) { Win = Hin; Wout = Hout; }
+    if (unpadded && Win == Hin && misc_conv0_reads_unpadded(B, Hin, C, k, Cout)) {
         if (s < 1 || s > 4) return SPAIR_ERR_UNSUPPORTED;
         if (out_bf16 && Cout == 128 && s == 2 && (Hin & 1) == 0) {
             hipLaunchKernelGGL(k_conv0_fwd_c1k4_mfma, dim3((Hout + C0_ROWS - 1) / C0_ROWS, B), dim3(256), c0_mfma_xs_bytes(Hin) + 4 * 16 * C0_TP, st, x,
@@ -495,9 +498,9 @@ int misc_conv0_fwd(const float* x, const float* xp, const float* w, const float*
     }
     const size_t lds = (size_t)k * k * C * Cout * sizeof(float);
     if (lds > 64 * 1024) return SPAIR_ERR_UNSUPPORTED;
-    const long long total = (long long)B * Hout * Hout * (Cout / 4);
+    const long long total = (long long)B * Hout * Wout * (Cout / 4);
     const unsigned grid = (unsigned)min((long long)4096, (total + 255) / 256);
-    hipLaunchKernelGGL(k_conv0_fwd, dim3(grid), dim3(256), lds, st, xp, w, bias, out, B, Hin, C, k, s, Hout, Cout, out_bf16);
+    hipLaunchKernelGGL(k_conv0_fwd, dim3(grid), dim3(256), lds, st, xp, w, bias, out, B, Hin, Win, C, k, s, Hout, Wout, Cout, out_bf16);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }

@@ -1,15 +1,17 @@
 // The renderer's host interface (K6, models.py:485-547).  A launcher runs its own kernel family only (SPAIR_ERR_UNSUPPORTED where its
 // _supported predicate refuses); the caller chooses the family: render_plan for the training step, the unit entry points (render.hip) for
-// the C ABI.  s16: fp16 (grey, alpha) sprites, ld_s in elements of that type; aux: B*C*I*I float2 (dBCE/dpre / D, pre); inv_den: B*I*I 1/D.
+// the C ABI.  s16: fp16 (grey, alpha) sprites, ld_s in elements of that type; aux: B*C*I*Iw float2 (dBCE/dpre / D, pre); inv_den: B*I*Iw 1/D.
+// The canvas is I rows x Iw columns; only the first generation (grey) and the generic-channel kernels take Iw != I.
 #pragma once
 #include "layout.h"
 
 struct RenderGeom {           // the objects: nbox [N][4], pres / depth with row stride ld_pd, N = B * HW rows
     const float *nbox, *pres, *depth;
     int ld_pd, B, HW, I, P, ac;
+    int Iw;                   // canvas width (I: its height)
 };
 
-int render_num_blocks(int B, int I);           // forward workgroups = bce_partial entries
+int render_num_blocks(int B, int I, int Iw);   // forward workgroups = bce_partial entries (first generation / colour: 16 x 16 tiles of I x Iw)
 int render_sprite_act(float* S, int ld, int N, int per, int CH, float obj_scale, float alpha_scale, float alpha_bias, hipStream_t s);
 int render_prep_bytes(int B, int HW);
 

@@ -34,13 +34,13 @@ template <bool S16>
 __global__ __launch_bounds__(256) void k_render_fwd(const float* __restrict__ S, int ld_s, const float* __restrict__ nbox,
                                                     const float* __restrict__ pres, const float* __restrict__ depth, int ld_pd,
                                                     const float* __restrict__ x, float* __restrict__ recon, float2* __restrict__ aux,
-                                                    float* __restrict__ bce_partial, int B, int HW, int I, int P, int ac,
+                                                    float* __restrict__ bce_partial, int B, int HW, int I, int Iw, int P, int ac,
                                                     float* __restrict__ inv_den) {
     __shared__ Cand cand[RCH];
     __shared__ unsigned short wlist[4][RCH];     // per wave (= a 16 x 4 pixel strip of the tile): the candidates that reach its rows
     __shared__ int wave_cnt[4][5];               // [culling wave][tile, strip 0..3]
     __shared__ float red[4];
-    const int tiles_x = (I + RT - 1) / RT, tiles = tiles_x * tiles_x;
+    const int tiles_x = (Iw + RT - 1) / RT, tiles = tiles_x * ((I + RT - 1) / RT);     // canvas I rows x Iw columns
     int b, tile;
     if ((B & 7) == 0) {   // XCD-aware: blocks id, id+8, ... share an XCD (round-robin dispatch)
         const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
@@ -53,12 +53,12 @@ __global__ __launch_bounds__(256) void k_render_fwd(const float* __restrict__ S,
     const int tx0 = (tile % tiles_x) * RT, ty0 = (tile / tiles_x) * RT;
     const int lx = threadIdx.x & (RT - 1), ly = threadIdx.x >> 4;
     const int px = tx0 + lx, py = ty0 + ly;
-    const bool inside = px < I && py < I;
-    const int tx1 = min(tx0 + RT, I) - 1, ty1 = min(ty0 + RT, I) - 1;
+    const bool inside = px < Iw && py < I;
+    const int tx1 = min(tx0 + RT, Iw) - 1, ty1 = min(ty0 + RT, I) - 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
     float num = 0.f, den = 0.f;
-    const float bX = stn_base(min(px, I - 1), I, ac), bY = stn_base(min(py, I - 1), I, ac);   // this pixel's base coordinate, once
+    const float bX = stn_base(min(px, Iw - 1), Iw, ac), bY = stn_base(min(py, I - 1), I, ac);   // this pixel's base coordinate, once
     for (int k0 = 0; k0 < HW; k0 += RCH) {
         // ---- cull RCH objects against this tile
         const int k = k0 + threadIdx.x;
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void k_render_fwd(const float* __restrict__ S,
             c.ax = 1.f / nb.z; c.bx = -tx / nb.z; c.ay = 1.f / nb.w; c.by = -ty / nb.w;
             c.pres = pres[(size_t)r * ld_pd]; c.depth = depth[(size_t)r * ld_pd]; c.row = r;
             // the zero-padded sprite is non-zero for source coords in (-1, P)
-            hit = src_of(c.ax, c.bx, tx1, I, P, ac) > -1.f && src_of(c.ax, c.bx, tx0, I, P, ac) < (float)P &&
+            hit = src_of(c.ax, c.bx, tx1, Iw, P, ac) > -1.f && src_of(c.ax, c.bx, tx0, Iw, P, ac) < (float)P &&
                   src_of(c.ay, c.by, ty1, I, P, ac) > -1.f && src_of(c.ay, c.by, ty0, I, P, ac) < (float)P;
         }
         // a second, finer cull per wave strip: at 16 x 16 a tile meets ~25 of 256 objects, a pixel ~9; the 4-row strips drop a
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void k_render_fwd(const float* __restrict__ S,
         const float invD = 1.f / D;
         const float pre = num * invD;
         const float r = fminf(fmaxf(pre, 0.f), 1.f);
-        const size_t pi = ((size_t)b * I + py) * I + px;
+        const size_t pi = ((size_t)b * I + py) * Iw + px;
         const float xv = x[pi];
         recon[pi] = r;
         // torch BCE: log clamped at -100; backward denominator max(r(1-r), 1e-12)
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(RB_T) __attribute__((amdgpu_waves_per_eu(5, 5))) vo
                                                      const float* __restrict__ pres, const float* __restrict__ depth, int ld_pd,
                                                      const float2* __restrict__ aux, const float* __restrict__ gloss,
                                                      float* __restrict__ dlogits, float* __restrict__ dnbox, float* __restrict__ dpres,
-                                                     float* __restrict__ ddepth, int ld_g, int B, int HW, int I, int P, int ac,
+                                                     float* __restrict__ ddepth, int ld_g, int B, int HW, int I, int Iw, int P, int ac,
                                                      float obj_scale, float alpha_scale, int g_bf16) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     __shared__ float red[RB_WAVES][6];
@@ -214,15 +214,17 @@ __global__ __launch_bounds__(RB_T) __attribute__((amdgpu_waves_per_eu(5, 5))) vo
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     float4* Ssh = reinterpret_cast<float4*>(sm);             // (grey, alpha, importance, -)
     float* pb = reinterpret_cast<float*>(Ssh + NTX);          // staged per-pixel adjoints [RB_CAP][3]
-    float* btab = pb + 3 * RB_CAP;                            // base coordinate of output index j (no division per pixel)
-    for (int e = tid; e < I; e += RB_T) btab[e] = stn_base(e, I, ac);
+    float* btab = pb + 3 * RB_CAP;                            // base coordinate of output column j (no division per pixel)
+    float* btab_y = I == Iw ? btab : btab + Iw;               // ... and of output row j (its own table only when the canvas is not square)
+    for (int e = tid; e < Iw; e += RB_T) btab[e] = stn_base(e, Iw, ac);
+    if (I != Iw) for (int e = tid; e < I; e += RB_T) btab_y[e] = stn_base(e, I, ac);
     // (sample, object) of this workgroup: grid = (B, HW); consecutive workgroup ids walk the samples, so with B % 8 == 0
     // every object of sample b lands on XCD b % 8
     const int b = blockIdx.x, k = blockIdx.y;
     const int r = k * B + b;
     const float pr = pres[(size_t)r * ld_pd], dp = depth[(size_t)r * ld_pd], pd = pr * dp;
     const float gl = *gloss;
-    const float2* auxb = aux + (size_t)b * I * I;
+    const float2* auxb = aux + (size_t)b * I * Iw;
     const float mult = ac ? 0.5f * (float)(P - 1) : 0.5f * (float)P;
     // The object's geometry is the same for every thread, and gfx9 has no scalar float ALU: computed by all four waves it is ~300
     // VALU instructions per wave and object in a kernel that is VALU-issue bound.  Wave 0 computes it while the others already
@@ -232,12 +234,12 @@ __global__ __launch_bounds__(RB_T) __attribute__((amdgpu_waves_per_eu(5, 5))) vo
         const float tx = 2.f * nb.x - 1.f, ty = 2.f * nb.y - 1.f;
         const float ax_ = 1.f / nb.z, bx_ = -tx / nb.z, ay_ = 1.f / nb.w, by_ = -ty / nb.w;
         float sx0_, sxa_, sy0_, sya_;
-        src_affine(ax_, bx_, I, P, ac, sx0_, sxa_);
+        src_affine(ax_, bx_, Iw, P, ac, sx0_, sxa_);
         src_affine(ay_, by_, I, P, ac, sy0_, sya_);
         const float isx_ = __builtin_amdgcn_rcpf(sxa_), isy_ = __builtin_amdgcn_rcpf(sya_);   // only used for (conservative) index bounds
         int TU_ = P, TV_ = P;                                     // texel tile whose pixel footprint fits the staging buffer
-        while (rb_span(TU_, isx_, I) * rb_span(TV_, isy_, I) > RB_CAP && rb_sweeps(TU_, TV_) > 1) {
-            if (rb_span(TV_, isy_, I) >= rb_span(TU_, isx_, I) && TV_ > 1) TV_ = (TV_ + 1) >> 1;
+        while (rb_span(TU_, isx_, Iw) * rb_span(TV_, isy_, I) > RB_CAP && rb_sweeps(TU_, TV_) > 1) {
+            if (rb_span(TV_, isy_, I) >= rb_span(TU_, isx_, Iw) && TV_ > 1) TV_ = (TV_ + 1) >> 1;
             else if (TU_ > 1) TU_ = (TU_ + 1) >> 1;
             else TV_ = (TV_ + 1) >> 1;
         }
@@ -289,11 +291,11 @@ __global__ __launch_bounds__(RB_T) __attribute__((amdgpu_waves_per_eu(5, 5))) vo
     for (int tu0 = 0; tu0 < P; tu0 += TU) {
         const int tu1 = min(tu0 + TU, P), tv1 = min(tv0 + TV, P);      // texel tile [tu0,tu1) x [tv0,tv1)
         // pixels whose source coordinate lies in (tu0-1, tu1) x (tv0-1, tv1), one spare pixel either side
-        const int PX0 = max((int)floorf(((float)(tu0 - 1) - sx0) * isx), 0), PX1 = min((int)ceilf(((float)tu1 - sx0) * isx), I - 1);
+        const int PX0 = max((int)floorf(((float)(tu0 - 1) - sx0) * isx), 0), PX1 = min((int)ceilf(((float)tu1 - sx0) * isx), Iw - 1);
         const int PY0 = max((int)floorf(((float)(tv0 - 1) - sy0) * isy), 0), PY1 = min((int)ceilf(((float)tv1 - sy0) * isy), I - 1);
         const int pw = PX1 - PX0 + 1, ph = PY1 - PY0 + 1;
         const bool empty = pw <= 0 || ph <= 0;
-        const int rows_per = empty ? 1 : max(1, RB_CAP / pw);           // host guarantees I <= RB_CAP
+        const int rows_per = empty ? 1 : max(1, RB_CAP / pw);           // host guarantees Iw <= RB_CAP
         const bool multi = !empty && ph > rows_per;                      // only reachable when pass B is a single sweep
         float a0 = 0.f, a1 = 0.f, a2 = 0.f;
         const int wsh = rb_lane_shift(pw), W = 1 << wsh, RPI = 64 >> wsh;
@@ -317,19 +319,19 @@ __global__ __launch_bounds__(RB_T) __attribute__((amdgpu_waves_per_eu(5, 5))) vo
             if (wave < nj) {
                 int px, py;
                 pixel_of(wave, px, py);
-                avn = auxb[min(py, cy1) * I + min(px, PX1)];
+                avn = auxb[min(py, cy1) * Iw + min(px, PX1)];
             }
             for (int j = wave; j < nj; j += RB_WAVES) {
                 const float2 av = avn;                                   // (dBCE/dpre / D, pre)
                 int px, py;
                 {
                     pixel_of(min(j + RB_WAVES, nj - 1), px, py);
-                    avn = auxb[min(py, cy1) * I + min(px, PX1)];
+                    avn = auxb[min(py, cy1) * Iw + min(px, PX1)];
                 }
                 pixel_of(j, px, py);
                 if (py > cy1 || px > PX1) continue;
                 float gxn, gyn;
-                const float sx = src_from_base(ax, bx, btab[px], P, ac, gxn), sy = src_from_base(ay, by, btab[py], P, ac, gyn);
+                const float sx = src_from_base(ax, bx, btab[px], P, ac, gxn), sy = src_from_base(ay, by, btab_y[py], P, ac, gyn);
                 const bool inside = sx > -1.f && sx < (float)P && sy > -1.f && sy < (float)P;
                 const float fx = fminf(fmaxf(floorf(sx), -1.f), (float)(P - 1)), fy = fminf(fmaxf(floorf(sy), -1.f), (float)(P - 1));
                 const float wx1 = sx - fx, wy1 = sy - fy, wx0 = 1.f - wx1, wy0 = 1.f - wy1;
@@ -369,7 +371,7 @@ __global__ __launch_bounds__(RB_T) __attribute__((amdgpu_waves_per_eu(5, 5))) vo
                     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
                     for (int py = ya; py <= ye; ++py) {
                         float gdum;
-                        const float wy = fmaxf(1.f - fabsf(src_from_base(ay, by, btab[py], P, ac, gdum) - (float)v), 0.f);
+                        const float wy = fmaxf(1.f - fabsf(src_from_base(ay, by, btab_y[py], P, ac, gdum) - (float)v), 0.f);
                         const float* q = pb + ((py - cy0) * pw - PX0) * 3;
                         for (int px = xa; px <= xe; ++px) {
                             const float w = wy * fmaxf(1.f - fabsf(src_from_base(ax, bx, btab[px], P, ac, gdum) - (float)u), 0.f);
@@ -428,15 +430,14 @@ int render_sprite_act(float* S, int ld, int N, int per, int CH, float obj_scale,
     return SPAIR_OK;
 }
 
-int render_num_blocks(int B, int I) {
-    const int t = (I + RT - 1) / RT;
-    return B * t * t;
+int render_num_blocks(int B, int I, int Iw) {
+    return B * ((I + RT - 1) / RT) * ((Iw + RT - 1) / RT);
 }
 
 int render_fwd1(const RenderGeom& g, const float* S, int ld_s, int s16, const float* x, float* recon, float* aux, float* bce_partial,
                 float* inv_den, hipStream_t s) {
-    hipLaunchKernelGGL(s16 ? k_render_fwd<true> : k_render_fwd<false>, dim3(render_num_blocks(g.B, g.I)), dim3(256), 0, s, S, ld_s, g.nbox,
-                       g.pres, g.depth, g.ld_pd, x, recon, reinterpret_cast<float2*>(aux), bce_partial, g.B, g.HW, g.I, g.P, g.ac, inv_den);
+    hipLaunchKernelGGL(s16 ? k_render_fwd<true> : k_render_fwd<false>, dim3(render_num_blocks(g.B, g.I, g.Iw)), dim3(256), 0, s, S, ld_s,
+                       g.nbox, g.pres, g.depth, g.ld_pd, x, recon, reinterpret_cast<float2*>(aux), bce_partial, g.B, g.HW, g.I, g.Iw, g.P, g.ac, inv_den);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
@@ -444,26 +445,29 @@ int render_fwd1(const RenderGeom& g, const float* S, int ld_s, int s16, const fl
 int render_bwd1(const RenderGeom& g, const float* S, int ld_s, int s16, const float* aux, const float* gloss, float* dlogits, float* dnbox,
                 float* dpres, float* ddepth, int ld_g, float obj_scale, float alpha_scale, int g16, hipStream_t s) {
     if ((ld_s & 1) || (ld_g & 1)) return SPAIR_ERR_ALIGN;
-    if (g.I > RB_CAP || (long long)g.I * g.I > 0x7fffffffLL / 4 || g.HW > 65535) return SPAIR_ERR_UNSUPPORTED;
-    const size_t lds = ((size_t)(g.P + 2) * (g.P + 2) * 4 + 3 * RB_CAP + g.I) * sizeof(float);
+    if (g.I > RB_CAP || g.Iw > RB_CAP || (long long)g.I * g.Iw > 0x7fffffffLL / 4 || g.HW > 65535) return SPAIR_ERR_UNSUPPORTED;
+    const size_t lds = ((size_t)(g.P + 2) * (g.P + 2) * 4 + 3 * RB_CAP + g.Iw + (g.I != g.Iw ? g.I : 0)) * sizeof(float);
     if (lds > 65536) return SPAIR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(s16 ? k_render_bwd<true> : k_render_bwd<false>, dim3(g.B, g.HW), dim3(RB_T), lds, s, S, ld_s, g.nbox, g.pres, g.depth,
-                       g.ld_pd, reinterpret_cast<const float2*>(aux), gloss, dlogits, dnbox, dpres, ddepth, ld_g, g.B, g.HW, g.I, g.P, g.ac,
-                       obj_scale, alpha_scale, g16);
+                       g.ld_pd, reinterpret_cast<const float2*>(aux), gloss, dlogits, dnbox, dpres, ddepth, ld_g, g.B, g.HW, g.I, g.Iw, g.P,
+                       g.ac, obj_scale, alpha_scale, g16);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
 
 // The training step's renderer: in each direction the first family whose predicate accepts.  The workspace's
 // buffers share its base's alignment, so when the records are not written for an unaligned base, k_render_bwd2 refuses the sprites too.
+// A rectangular canvas (g.Iw != g.I) runs on the first generation (grey) or the colour kernels: records, the matrix-core forward and the
+// second generation are square-only and are refused here, whatever their predicates (which only see g.I) say.
 RenderPlan render_plan(const SpairDims& d, const RenderGeom& g, int ld_s, const float* S, const void* rec, const float* dlogits) {
     RenderPlan p;
+    const bool square = g.Iw == g.I;
     p.s16 = p.g16 = render_16bit(d);
-    p.rec = p.s16 && render_prep_supported(g) && !(reinterpret_cast<uintptr_t>(rec) & 15);
+    p.rec = p.s16 && square && render_prep_supported(g) && !(reinterpret_cast<uintptr_t>(rec) & 15);
     p.fwd = d.C != 1 ? RENDER_COLOUR
           : p.rec && render_fwd_mma_supported(g, S, ld_s, rec) ? RENDER_MMA
-          : render_fwd2_supported(g, S, ld_s, p.s16) ? RENDER_GEN2 : RENDER_GEN1;
-    p.bwd = d.C != 1 ? RENDER_COLOUR : p.s16 && render_bwd2_supported(g, S, ld_s, dlogits, ld_s) ? RENDER_GEN2 : RENDER_GEN1;
+          : square && render_fwd2_supported(g, S, ld_s, p.s16) ? RENDER_GEN2 : RENDER_GEN1;
+    p.bwd = d.C != 1 ? RENDER_COLOUR : square && p.s16 && render_bwd2_supported(g, S, ld_s, dlogits, ld_s) ? RENDER_GEN2 : RENDER_GEN1;
     return p;
 }
 
@@ -487,14 +491,14 @@ static int render_bwd_grey(const RenderGeom& g, const float* S, int ld_s, int b1
 extern "C" int spair_render_fwd(const float* sprites, int ld_s, const float* nbox, const float* pres, const float* depth,
                                 const float* x, float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P,
                                 int align_corners, void* stream) {
-    return render_fwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners}, sprites, ld_s, 0, C, x, recon, aux, bce_partial,
+    return render_fwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners, I}, sprites, ld_s, 0, C, x, recon, aux, bce_partial,
                            (hipStream_t)stream);
 }
 extern "C" int spair_render_bwd(const float* sprites, int ld_s, const float* nbox, const float* pres, const float* depth,
                                 const float* aux, const float* grad_loss, float* dlogits, float* dnbox, float* dpres,
                                 float* ddepth, int B, int HW, int C, int I, int P, int align_corners, float obj_scale,
                                 float alpha_scale, void* stream) {
-    return render_bwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners}, sprites, ld_s, 0, nullptr, C, aux, grad_loss, dlogits, dnbox,
+    return render_bwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners, I}, sprites, ld_s, 0, nullptr, C, aux, grad_loss, dlogits, dnbox,
                            dpres, ddepth, obj_scale, alpha_scale, (hipStream_t)stream);
 }
 
@@ -503,14 +507,14 @@ extern "C" int spair_render_bwd(const float* sprites, int ld_s, const float* nbo
 extern "C" int spair_render_fwd16(const void* sprites_f16, int ld_s, const float* nbox, const float* pres, const float* depth,
                                   const float* x, float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P,
                                   int align_corners, void* stream) {
-    return render_fwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners}, reinterpret_cast<const float*>(sprites_f16), ld_s, 1, C, x,
+    return render_fwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners, I}, reinterpret_cast<const float*>(sprites_f16), ld_s, 1, C, x,
                            recon, aux, bce_partial, (hipStream_t)stream);
 }
 extern "C" int spair_render_bwd16(const void* sprites_f16, int ld_s, const float* nbox, const float* pres, const float* depth,
                                   const float* aux, const float* grad_loss, void* dlogits_bf16, float* dnbox, float* dpres,
                                   float* ddepth, int B, int HW, int C, int I, int P, int align_corners, float obj_scale,
                                   float alpha_scale, void* stream) {
-    return render_bwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners}, reinterpret_cast<const float*>(sprites_f16), ld_s, 1, nullptr,
+    return render_bwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners, I}, reinterpret_cast<const float*>(sprites_f16), ld_s, 1, nullptr,
                            C, aux, grad_loss, reinterpret_cast<float*>(dlogits_bf16), dnbox, dpres, ddepth, obj_scale, alpha_scale,
                            (hipStream_t)stream);
 }
@@ -520,13 +524,13 @@ extern "C" int spair_render_bwd16(const void* sprites_f16, int ld_s, const float
 extern "C" int spair_render_prep(const float* nbox, const float* pres, const float* depth, void* records, int B, int HW, int I, int P,
                                  int align_corners, void* stream) {
     if (B <= 0 || HW <= 0 || I <= 0) return SPAIR_ERR_SHAPE;
-    return render_prep({nbox, pres, depth, 1, B, HW, I, P, align_corners}, records, (hipStream_t)stream);
+    return render_prep({nbox, pres, depth, 1, B, HW, I, P, align_corners, I}, records, (hipStream_t)stream);
 }
 extern "C" int spair_render_fwd16m(const void* sprites_f16, int ld_s, const void* records, const float* x, float* recon, float* aux,
                                    float* bce_partial, int B, int HW, int C, int I, int P, int align_corners, void* stream) {
     if (C != 1) return SPAIR_ERR_UNSUPPORTED;
     if (B <= 0 || HW <= 0 || I <= 0) return SPAIR_ERR_SHAPE;
-    return render_fwd_mma({nullptr, nullptr, nullptr, 1, B, HW, I, P, align_corners}, sprites_f16, ld_s, records, x, recon, aux, bce_partial,
+    return render_fwd_mma({nullptr, nullptr, nullptr, 1, B, HW, I, P, align_corners, I}, sprites_f16, ld_s, records, x, recon, aux, bce_partial,
                           nullptr, (hipStream_t)stream);
 }
 // spair_render_bwd16 reading the inverse-affine parameters and pixel footprints from the records spair_render_prep wrote for the same nbox /
@@ -535,7 +539,7 @@ extern "C" int spair_render_bwd16r(const void* sprites_f16, int ld_s, const floa
                                    const void* records, const float* aux, const float* grad_loss, void* dlogits_bf16, float* dnbox,
                                    float* dpres, float* ddepth, int B, int HW, int C, int I, int P, int align_corners, float obj_scale,
                                    float alpha_scale, void* stream) {
-    return render_bwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners}, reinterpret_cast<const float*>(sprites_f16), ld_s, 1, records,
+    return render_bwd_grey({nbox, pres, depth, 1, B, HW, I, P, align_corners, I}, reinterpret_cast<const float*>(sprites_f16), ld_s, 1, records,
                            C, aux, grad_loss, reinterpret_cast<float*>(dlogits_bf16), dnbox, dpres, ddepth, obj_scale, alpha_scale,
                            (hipStream_t)stream);
 }

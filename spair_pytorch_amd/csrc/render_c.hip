@@ -21,22 +21,22 @@ template <int C>
 __global__ __launch_bounds__(256) void k_render_fwd_c(const float* __restrict__ S, int ld_s, const float* __restrict__ nbox,
                                                       const float* __restrict__ pres, const float* __restrict__ depth, int ld_pd,
                                                       const float* __restrict__ x, float* __restrict__ recon, float2* __restrict__ aux,
-                                                      float* __restrict__ bce_partial, int B, int HW, int I, int P, int ac,
+                                                      float* __restrict__ bce_partial, int B, int HW, int I, int Iw, int P, int ac,
                                                       float* __restrict__ inv_den) {
     constexpr int CH = C + 1;
     __shared__ Cand cand[RCH];
     __shared__ float red[4];
-    const int tiles_x = (I + RT - 1) / RT, tiles = tiles_x * tiles_x;
+    const int tiles_x = (Iw + RT - 1) / RT, tiles = tiles_x * ((I + RT - 1) / RT);     // canvas I rows x Iw columns
     const int b = blockIdx.x / tiles, tile = blockIdx.x % tiles;
     const int tx0 = (tile % tiles_x) * RT, ty0 = (tile / tiles_x) * RT;
     const int lx = threadIdx.x & (RT - 1), ly = threadIdx.x >> 4;
     const int px = tx0 + lx, py = ty0 + ly;
-    const bool inside = px < I && py < I;
-    const int tx1 = min(tx0 + RT, I) - 1, ty1 = min(ty0 + RT, I) - 1;
+    const bool inside = px < Iw && py < I;
+    const int tx1 = min(tx0 + RT, Iw) - 1, ty1 = min(ty0 + RT, I) - 1;
     float num[C], den = 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c) num[c] = 0.f;
-    const float bX = stn_base(min(px, I - 1), I, ac), bY = stn_base(min(py, I - 1), I, ac);
+    const float bX = stn_base(min(px, Iw - 1), Iw, ac), bY = stn_base(min(py, I - 1), I, ac);
     for (int k0 = 0; k0 < HW; k0 += RCH) {
         const int k = k0 + threadIdx.x;
         if (k < HW) {
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void k_render_fwd_c(const float* __restrict__ 
             Cand c;
             c.ax = 1.f / nb.z; c.bx = -tx / nb.z; c.ay = 1.f / nb.w; c.by = -ty / nb.w;
             c.pres = pres[(size_t)r * ld_pd]; c.depth = depth[(size_t)r * ld_pd]; c.row = r;
-            const bool hit = src_of(c.ax, c.bx, tx1, I, P, ac) > -1.f && src_of(c.ax, c.bx, tx0, I, P, ac) < (float)P &&
+            const bool hit = src_of(c.ax, c.bx, tx1, Iw, P, ac) > -1.f && src_of(c.ax, c.bx, tx0, Iw, P, ac) < (float)P &&
                              src_of(c.ay, c.by, ty1, I, P, ac) > -1.f && src_of(c.ay, c.by, ty0, I, P, ac) < (float)P;
             if (!hit) c.row = -1;                     // (every thread its own slot: the order of the sums is the object order)
             cand[threadIdx.x] = c;
@@ -92,12 +92,12 @@ __global__ __launch_bounds__(256) void k_render_fwd_c(const float* __restrict__ 
     if (inside) {
         const float D = den + (float)HW * 1e-9f;          // every object adds 1e-9 (models.py:527)
         const float invD = 1.f / D;
-        if (inv_den) inv_den[((size_t)b * I + py) * I + px] = invD;      // one denominator per pixel, shared by the colour channels
+        if (inv_den) inv_den[((size_t)b * I + py) * Iw + px] = invD;      // one denominator per pixel, shared by the colour channels
 #pragma unroll
         for (int c = 0; c < C; ++c) {
             const float pre = num[c] * invD;
             const float r = fminf(fmaxf(pre, 0.f), 1.f);
-            const size_t pi = (((size_t)b * C + c) * I + py) * I + px;
+            const size_t pi = (((size_t)b * C + c) * I + py) * Iw + px;
             const float xv = x[pi];
             recon[pi] = r;
             bce += -(xv * fmaxf(logf(r), -100.f) + (1.f - xv) * fmaxf(logf(1.f - r), -100.f));      // torch BCE: log clamped at -100
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(64) void k_render_bwd_c(const float* __restrict__ S
                                                      const float* __restrict__ pres, const float* __restrict__ depth, int ld_pd,
                                                      const float2* __restrict__ aux, const float* __restrict__ gloss,
                                                      float* __restrict__ dlogits, float* __restrict__ dnbox, float* __restrict__ dpres,
-                                                     float* __restrict__ ddepth, int ld_g, int B, int HW, int I, int P, int ac,
+                                                     float* __restrict__ ddepth, int ld_g, int B, int HW, int I, int Iw, int P, int ac,
                                                      float obj_scale, float alpha_scale) {
     constexpr int CH = C + 1, NA = C + 2;        // texel channels; adjoint channels (colour.., alpha * pres, importance)
     extern __shared__ float acc[];               // [P * P][NA]
@@ -131,12 +131,12 @@ __global__ __launch_bounds__(64) void k_render_bwd_c(const float* __restrict__ S
     const float mult = ac ? 0.5f * (float)(P - 1) : 0.5f * (float)P;
     // pixel footprint: the indices whose source coordinate lies in (-1, P), exact w.r.t. the forward's own coordinate formula
     float sx0, sxa, sy0, sya;
-    src_affine(ax, bx, I, P, ac, sx0, sxa);
+    src_affine(ax, bx, Iw, P, ac, sx0, sxa);
     src_affine(ay, by, I, P, ac, sy0, sya);
     int PX0, PX1, PY0, PY1;
-    const float inv_I = 1.f / (float)I;
-    if (ac) { rb2_range<1, 0>(ax, bx, sx0, 1.f / sxa, I, inv_I, P, PX0, PX1); rb2_range<1, 0>(ay, by, sy0, 1.f / sya, I, inv_I, P, PY0, PY1); }
-    else { rb2_range<0, 0>(ax, bx, sx0, 1.f / sxa, I, inv_I, P, PX0, PX1); rb2_range<0, 0>(ay, by, sy0, 1.f / sya, I, inv_I, P, PY0, PY1); }
+    const float inv_I = 1.f / (float)I, inv_Iw = 1.f / (float)Iw;
+    if (ac) { rb2_range<1, 0>(ax, bx, sx0, 1.f / sxa, Iw, inv_Iw, P, PX0, PX1); rb2_range<1, 0>(ay, by, sy0, 1.f / sya, I, inv_I, P, PY0, PY1); }
+    else { rb2_range<0, 0>(ax, bx, sx0, 1.f / sxa, Iw, inv_Iw, P, PX0, PX1); rb2_range<0, 0>(ay, by, sy0, 1.f / sya, I, inv_I, P, PY0, PY1); }
     const int pw = max(PX1 - PX0 + 1, 0), ph = max(PY1 - PY0 + 1, 0);
     const float* sp = S + (size_t)r * ld_s;
     __builtin_amdgcn_s_waitcnt(0xc07f);      // this lane's zeroing stores
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(64) void k_render_bwd_c(const float* __restrict__ S
         const int iy = min(idx, pw * ph - 1) / pw, ix = min(idx, pw * ph - 1) - iy * pw;
         const int px = PX0 + ix, py = PY0 + iy;
         float gnx, gny;
-        const float sx = src_from_base(ax, bx, stn_base(px, I, ac), P, ac, gnx), sy = src_from_base(ay, by, stn_base(py, I, ac), P, ac, gny);
+        const float sx = src_from_base(ax, bx, stn_base(px, Iw, ac), P, ac, gnx), sy = src_from_base(ay, by, stn_base(py, I, ac), P, ac, gny);
         const bool cov = live && sx > -1.f && sx < (float)P && sy > -1.f && sy < (float)P;
         const float fx = floorf(sx), fy = floorf(sy);
         const int x0 = (int)fx, y0 = (int)fy;
@@ -176,10 +176,10 @@ __global__ __launch_bounds__(64) void k_render_bwd_c(const float* __restrict__ S
         }
         float d_g[C], d_a = 0.f, d_m = 0.f;
         {
-            const size_t pix = (size_t)py * I + px;
+            const size_t pix = (size_t)py * Iw + px;
 #pragma unroll
             for (int c = 0; c < C; ++c) {
-                const float2 av = cov ? aux[((size_t)b * C + c) * I * I + pix] : make_float2(0.f, 0.f);
+                const float2 av = cov ? aux[((size_t)b * C + c) * I * Iw + pix] : make_float2(0.f, 0.f);
                 const float go = av.x * gl;        // dBCE/dpre_c / D
                 const float tq = go * (m + 1e-9f);
                 d_g[c] = tq * a;
@@ -233,13 +233,13 @@ __global__ __launch_bounds__(64) void k_render_bwd_c(const float* __restrict__ S
 
 }  // namespace
 
-// sprites fp32 [N][ld_s] = [P*P][C+1]; x / recon [B][C][I][I]; aux: B*C*I*I float2 (dBCE/dpre / D, pre) or null; inv_den: B*I*I 1/D or null
+// sprites fp32 [N][ld_s] = [P*P][C+1]; x / recon [B][C][I][Iw]; aux: B*C*I*Iw float2 (dBCE/dpre / D, pre) or null; inv_den: B*I*Iw 1/D or null
 int render_fwd_c(const RenderGeom& g, const float* S, int ld_s, int C, const float* x, float* recon, float* aux, float* bce_partial,
                  float* inv_den, hipStream_t s) {
     if (C < 2 || C > RC_MAXC) return SPAIR_ERR_UNSUPPORTED;
     if (g.B <= 0 || g.HW <= 0 || g.I <= 0 || g.P <= 0 || ld_s < g.P * g.P * (C + 1)) return SPAIR_ERR_SHAPE;
-    hipLaunchKernelGGL(C == 2 ? k_render_fwd_c<2> : k_render_fwd_c<3>, dim3(render_num_blocks(g.B, g.I)), dim3(256), 0, s, S, ld_s, g.nbox,
-                       g.pres, g.depth, g.ld_pd, x, recon, reinterpret_cast<float2*>(aux), bce_partial, g.B, g.HW, g.I, g.P, g.ac, inv_den);
+    hipLaunchKernelGGL(C == 2 ? k_render_fwd_c<2> : k_render_fwd_c<3>, dim3(render_num_blocks(g.B, g.I, g.Iw)), dim3(256), 0, s, S, ld_s,
+                       g.nbox, g.pres, g.depth, g.ld_pd, x, recon, reinterpret_cast<float2*>(aux), bce_partial, g.B, g.HW, g.I, g.Iw, g.P, g.ac, inv_den);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
@@ -249,11 +249,11 @@ int render_bwd_c(const RenderGeom& g, const float* S, int ld_s, int C, const flo
                  float* dpres, float* ddepth, int ld_g, float obj_scale, float alpha_scale, hipStream_t s) {
     const int B = g.B, HW = g.HW, I = g.I, P = g.P;
     if (C < 2 || C > RC_MAXC) return SPAIR_ERR_UNSUPPORTED;
-    if (B <= 0 || HW <= 0 || HW > 65535 || I <= 0 || P <= 0 || ld_s < P * P * (C + 1) || ld_g < P * P * (C + 1)) return SPAIR_ERR_SHAPE;
+    if (B <= 0 || HW <= 0 || HW > 65535 || I <= 0 || g.Iw <= 0 || P <= 0 || ld_s < P * P * (C + 1) || ld_g < P * P * (C + 1)) return SPAIR_ERR_SHAPE;
     const size_t lds = (size_t)P * P * (C + 2) * sizeof(float);
     if (lds > 64 * 1024) return SPAIR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(C == 2 ? k_render_bwd_c<2> : k_render_bwd_c<3>, dim3(B, HW), dim3(64), lds, s, S, ld_s, g.nbox, g.pres, g.depth, g.ld_pd,
-                       reinterpret_cast<const float2*>(aux), gloss, dlogits, dnbox, dpres, ddepth, ld_g, B, HW, I, P, g.ac, obj_scale, alpha_scale);
+                       reinterpret_cast<const float2*>(aux), gloss, dlogits, dnbox, dpres, ddepth, ld_g, B, HW, I, g.Iw, P, g.ac, obj_scale, alpha_scale);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
@@ -262,11 +262,11 @@ int render_bwd_c(const RenderGeom& g, const float* S, int ld_s, int C, const flo
 extern "C" int spair_render_fwd_rgb(const float* sprites, int ld_s, const float* nbox, const float* pres, const float* depth, const float* x,
                                     float* recon, float* aux, float* bce_partial, int B, int HW, int C, int I, int P, int align_corners,
                                     void* stream) {
-    return render_fwd_c({nbox, pres, depth, 1, B, HW, I, P, align_corners}, sprites, ld_s, C, x, recon, aux, bce_partial, nullptr, (hipStream_t)stream);
+    return render_fwd_c({nbox, pres, depth, 1, B, HW, I, P, align_corners, I}, sprites, ld_s, C, x, recon, aux, bce_partial, nullptr, (hipStream_t)stream);
 }
 extern "C" int spair_render_bwd_rgb(const float* sprites, int ld_s, const float* nbox, const float* pres, const float* depth, const float* aux,
                                     const float* grad_loss, float* dlogits, float* dnbox, float* dpres, float* ddepth, int B, int HW, int C,
                                     int I, int P, int align_corners, float obj_scale, float alpha_scale, void* stream) {
-    return render_bwd_c({nbox, pres, depth, 1, B, HW, I, P, align_corners}, sprites, ld_s, C, aux, grad_loss, dlogits, dnbox, dpres, ddepth, ld_s,
+    return render_bwd_c({nbox, pres, depth, 1, B, HW, I, P, align_corners, I}, sprites, ld_s, C, aux, grad_loss, dlogits, dnbox, dpres, ddepth, ld_s,
                         obj_scale, alpha_scale, (hipStream_t)stream);
 }

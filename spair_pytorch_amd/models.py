@@ -47,7 +47,8 @@ class SpairDims(ctypes.Structure):
                 ("alpha_logit_scale", ctypes.c_float), ("alpha_logit_bias", ctypes.c_float),
                 ("vae_beta", ctypes.c_float), ("prior_mean", ctypes.c_float * 6), ("prior_std", ctypes.c_float * 6),
                 ("obj_conv", ctypes.c_int), ("oc_n", ctypes.c_int), ("oc_k", ctypes.c_int * 4), ("oc_s", ctypes.c_int * 4),
-                ("oc_c", ctypes.c_int * 4), ("lookback", ctypes.c_int)]
+                ("oc_c", ctypes.c_int * 4), ("lookback", ctypes.c_int),
+                ("Iw", ctypes.c_int), ("Gw", ctypes.c_int), ("pad_post_w", ctypes.c_int)]
 
 
 class SpairStep(ctypes.Structure):
@@ -64,13 +65,17 @@ _DTYPES = {'f32': 0, 'fp32': 0, 'float32': 0, 'bf16': 1, 'bfloat16': 1}
 
 
 def make_dims(batch, image_shape, topology, dtype=None, object_conv_topology=None, lookback=1):
-    """``object_conv_topology``: the layer list of the convolutional object encoder / decoder variant (``None`` = the MLP pair)."""
+    """``object_conv_topology``: the layer list of the convolutional object encoder / decoder variant (``None`` = the MLP pair).
+    ``image_shape`` = [C, H, W]; H != W is a rectangular image (I, G, pad_post: the height axis; Iw, Gw, pad_post_w: the width axis)."""
     from .modules import backbone_geometry, _topology_conv_args
     d = SpairDims()
-    C, I, I2 = image_shape
-    assert I == I2, "square images only"
+    C, I, Iw = (int(v) for v in image_shape)
     pre, post, G, cell, _ = backbone_geometry(I, topology)
+    pre_w, post_w, Gw, cell_w, _ = backbone_geometry(Iw, topology)
+    assert (pre_w, cell_w) == (pre, cell)
     d.B, d.C, d.I, d.G = int(batch), int(C), int(I), int(G)
+    if Iw != I:      # (square: the three width fields stay 0 = "the same as I, G, pad_post", the C ABI's square meaning)
+        d.Iw, d.Gw, d.pad_post_w = Iw, int(Gw), int(post_w)
     d.P, d.A, d.F, d.NP = int(cfg.OBJECT_SHAPE[0]), int(cfg.N_ATTRIBUTES), int(cfg.N_BACKBONE_FEATURES), int(cfg.N_PASSTHROUGH_FEATURES)
     d.n_conv = len(topology)
     for i, layer in enumerate(topology):
@@ -93,6 +98,11 @@ def make_dims(batch, image_shape, topology, dtype=None, object_conv_topology=Non
         for i, layer in enumerate(object_conv_topology):
             d.oc_c[i], d.oc_k[i], d.oc_s[i] = _topology_conv_args(layer)
     return d
+
+
+def dims_width(d):
+    """(image width, grid width) of SpairDims d: its Iw / Gw, or I / G where those are 0 (a square image)."""
+    return (d.Iw or d.I), (d.Gw or d.G)
 
 
 def step_scalars(global_step, batch, world_size=1, train=True):
@@ -360,7 +370,7 @@ class SPAIR(nn.Module):
             if nbytes <= 0:
                 raise L.SpairHipError("unsupported configuration for the HIP engine (B=%d, image=%s, topology=%s)" %
                                       (batch, self.image_shape, self.backbone.topology))
-            G, A = d.G, d.A
+            (G, A), Gw = (d.G, d.A), dims_width(d)[1]
             dev = self.device
             limit = self.max_engines
             if limit is None:
@@ -384,8 +394,8 @@ class SPAIR(nn.Module):
             ws = block.zero_() if block is not None else torch.zeros(nbytes, dtype=torch.uint8, device=dev)
             e = _Engine(dims=d, generation=0,
                      workspace=ws,                                                   # zero-initialised ONCE per engine
-                     noise=dict(eps_box=torch.empty(batch, 4, G, G, device=dev), eps_attr=torch.empty(batch, A, G, G, device=dev),
-                                eps_depth=torch.empty(batch, 1, G, G, device=dev), u_pres=torch.empty(batch, 1, G, G, device=dev)))
+                     noise=dict(eps_box=torch.empty(batch, 4, G, Gw, device=dev), eps_attr=torch.empty(batch, A, G, Gw, device=dev),
+                                eps_depth=torch.empty(batch, 1, G, Gw, device=dev), u_pres=torch.empty(batch, 1, G, Gw, device=dev)))
             if self.differentiable_outputs:
                 self._outgrad_buffers(e)
         else:
@@ -398,12 +408,13 @@ class SPAIR(nn.Module):
         forward, and the backward's folded copy of the renderer's per-pixel adjoints (+ one float for its unit loss gradient)."""
         if e.get("inv_den") is None:
             d = e['dims']
-            e["inv_den"] = torch.empty(d.B, d.I, d.I, device=self.device, dtype=torch.float32)
-            e["aux_scratch"] = torch.empty(2 * d.B * d.C * d.I * d.I + 1, device=self.device, dtype=torch.float32)
+            Iw = dims_width(d)[0]
+            e["inv_den"] = torch.empty(d.B, d.I, Iw, device=self.device, dtype=torch.float32)
+            e["aux_scratch"] = torch.empty(2 * d.B * d.C * d.I * Iw + 1, device=self.device, dtype=torch.float32)
         return e["inv_den"], e["aux_scratch"]
 
     def _input_grad_scratch(self, e):
-        """Scratch of the image gradient of engine ``e`` (the glimpse term, [B,C,I,I] fp32), allocated on first use; never part of the
+        """Scratch of the image gradient of engine ``e`` (the glimpse term, [B,C,H,W] fp32), allocated on first use; never part of the
         workspace."""
         if e.get("x_scratch") is None:
             lib = L.lib()
@@ -425,11 +436,11 @@ class SPAIR(nn.Module):
         e = self._engine(x.shape[0])
         d = e['dims']
         dev = x.device
-        B, G = x.shape[0], d.G
+        (B, G), (Iw, Gw) = (x.shape[0], d.G), dims_width(d)
         loss_terms = torch.empty(16, device=dev, dtype=torch.float32)
-        recon = torch.empty(B, d.C, d.I, d.I, device=dev, dtype=torch.float32)
-        z_where = torch.empty(B, 4, G, G, device=dev, dtype=torch.float32)
-        z_pres = torch.empty(B, 1, G, G, device=dev, dtype=torch.float32)
+        recon = torch.empty(B, d.C, d.I, Iw, device=dev, dtype=torch.float32)
+        z_where = torch.empty(B, 4, G, Gw, device=dev, dtype=torch.float32)
+        z_pres = torch.empty(B, 1, G, Gw, device=dev, dtype=torch.float32)
         st = step_scalars(step, B, self.world_size, train)
         if noise.get('_seed') is not None:
             st.draw_noise, st.noise_seed = 1, int(noise['_seed'])
@@ -485,6 +496,10 @@ class SPAIR(nn.Module):
             noise = self._draw_noise(e)
         else:
             noise = {k: noise[k].to(x.device).contiguous().float() for k in ('eps_box', 'eps_attr', 'eps_depth', 'u_pres')}
+            want = {k: tuple(v.shape) for k, v in e['noise'].items()}      # [B,{4,A,1,1},Gh,Gw]
+            for k, v in noise.items():
+                if tuple(v.shape) != want[k]:
+                    raise AssertionError("noise[%r]: expected %s, got %s" % (k, want[k], tuple(v.shape)))
         self.training_wheel = exponential_decay(global_step, None, **cfg.LATENT_VAR_TRAINING_WHEEL_PARAM)
         if torch.is_grad_enabled():
             loss, recon, z_where, z_pres = _StepFn.apply(self._anchor, self, x, int(global_step), noise)
@@ -576,7 +591,7 @@ class SPAIR(nn.Module):
         e = self._last_engine()
         d = e['dims']
         ch = d.A if which in (0, 6, 12) else {0: 8, 1: 2 * d.A, 2: 2, 3: 1}[which % 100] if which >= 100 else 1
-        out = torch.empty(d.B, ch, d.G, d.G, device=self.device, dtype=torch.float32)
+        out = torch.empty(d.B, ch, d.G, dims_width(d)[1], device=self.device, dtype=torch.float32)
         L.check(L.lib().spair_export_map(ctypes.byref(d), L.ptr(e['workspace']), int(which), L.ptr(out), L.stream()), "spair_export_map")
         return out
 

@@ -96,10 +96,11 @@ class Backbone(Module):
             n_prev = f
         net['conv_out'] = Conv2d(in_channels=f, out_channels=n_out_channels, kernel_size=1, stride=1)
         self.net = Sequential(net)
-        pre, post, n, cell, _ = backbone_geometry(input_shape[-1], self.topology)
-        self.pad_pre, self.pad_post = pre, post
-        self.padding = nn.ZeroPad2d((pre, post, pre, post))
-        self.n_grid_cells = np.array([n, n])
+        pre, post, n, cell, _ = backbone_geometry(input_shape[-2], self.topology)        # per axis (height, width), modules.py:68-105
+        _, post_w, n_w, _, _ = backbone_geometry(input_shape[-1], self.topology)
+        self.pad_pre, self.pad_post, self.pad_post_w = pre, post, post_w
+        self.padding = nn.ZeroPad2d((pre, post_w, pre, post))
+        self.n_grid_cells = np.array([n, n_w])
         self.grid_cell_size = np.array([cell, cell])
         self.n_out_channels = n_out_channels
 
@@ -107,8 +108,7 @@ class Backbone(Module):
         """modules.py:32-41 -- the reference probes with a random image, which consumes the
         global RNG; the draw is replicated so later initialisers see the same stream."""
         torch.rand(1, *cfg.INPUT_IMAGE_SHAPE)
-        n = int(self.n_grid_cells[0])
-        return torch.Size([self.n_out_channels, n, n])
+        return torch.Size([self.n_out_channels, int(self.n_grid_cells[0]), int(self.n_grid_cells[1])])
 
     def forward(self, x):
         """modules.py:107-111 on its own: pad, then the conv stack as implicit GEMMs (spair_gemm_nt_conv, exact fp32 MFMA mode).
@@ -216,13 +216,14 @@ class _StnFn(torch.autograd.Function):
         img = image.detach().contiguous().float()
         zw = z_where.detach().contiguous().float()
         ac = int(cfg.ALIGN_CORNERS)
-        if inverse:
-            out = torch.empty(N, C, size, size, device=img.device, dtype=torch.float32)
-            L.check(L.lib().spair_stn_inverse_fwd(L.ptr(img), L.ptr(zw), L.ptr(out), N, C, H, size, ac, L.stream()), "spair_stn_inverse_fwd")
-        else:
+        if inverse:     # size = (canvas height, width); the sprites are square
+            out = torch.empty(N, C, size[0], size[1], device=img.device, dtype=torch.float32)
+            L.check(L.lib().spair_stn_inverse_fwd_hw(L.ptr(img), L.ptr(zw), L.ptr(out), N, C, H, size[0], size[1], ac, L.stream()),
+                    "spair_stn_inverse_fwd_hw")
+        else:           # size = the glimpse side; the image is H x W
             out = torch.empty(N, C * size * size, device=img.device, dtype=torch.float32)
-            L.check(L.lib().spair_stn_glimpse_fwd(L.ptr(img), L.ptr(zw), N, L.ptr(out), C * size * size, N, C, H, size, ac, L.stream()),
-                    "spair_stn_glimpse_fwd")
+            L.check(L.lib().spair_stn_glimpse_fwd_hw(L.ptr(img), L.ptr(zw), N, L.ptr(out), C * size * size, N, C, H, W, size, ac, L.stream()),
+                    "spair_stn_glimpse_fwd_hw")
             out = out.view(N, C, size, size)
         ctx.save_for_backward(img, zw)
         ctx.size, ctx.inverse = size, inverse
@@ -238,26 +239,30 @@ class _StnFn(torch.autograd.Function):
         dzw = torch.zeros(N, 4, device=img.device, dtype=torch.float32)
         if ctx.inverse:
             dimg = torch.zeros_like(img)
-            L.check(L.lib().spair_stn_inverse_bwd(L.ptr(img), L.ptr(zw), L.ptr(g), L.ptr(dimg), L.ptr(dzw), N, C, H, ctx.size, ac, L.stream()),
-                    "spair_stn_inverse_bwd")
+            L.check(L.lib().spair_stn_inverse_bwd_hw(L.ptr(img), L.ptr(zw), L.ptr(g), L.ptr(dimg), L.ptr(dzw), N, C, H, ctx.size[0], ctx.size[1],
+                                                     ac, L.stream()), "spair_stn_inverse_bwd_hw")
             return dimg, dzw, None, None
         per = C * ctx.size * ctx.size
-        L.check(L.lib().spair_stn_glimpse_bwd(L.ptr(img), L.ptr(zw), N, L.ptr(g.view(N, per)), per, L.ptr(dzw), N, C, H, ctx.size, ac,
-                                              L.stream()), "spair_stn_glimpse_bwd")
+        L.check(L.lib().spair_stn_glimpse_bwd_hw(L.ptr(img), L.ptr(zw), N, L.ptr(g.view(N, per)), per, L.ptr(dzw), N, C, H, W, ctx.size, ac,
+                                                 L.stream()), "spair_stn_glimpse_bwd_hw")
         return None, dzw, None, None
 
 
 def stn(image, z_where, output_dims, device=None, inverse=False):
-    """modules.py:216-273.  ``image`` [N,C,H,W] float32 on the GPU, ``z_where`` [N,4] = (xt,yt,xs,ys), square sizes.
-    Forward direction: glimpse extraction (border padding), differentiable wrt z_where.  ``inverse=True``: the sprites are placed
-    on an ``output_dims`` canvas through the inverse affine (zeros padding), differentiable wrt both arguments; this materialises
-    [N,C,I,I], which the training step itself never does (the renderer fuses it)."""
+    """modules.py:216-273.  ``image`` [N,C,H,W] float32 on the GPU, ``z_where`` [N,4] = (xt,yt,xs,ys).
+    Forward direction: glimpse extraction (border padding) from an H x W image (H != W allowed) into a square ``output_dims`` glimpse,
+    differentiable wrt z_where.  ``inverse=True``: the square sprites are placed on an ``output_dims = [H, W]`` canvas (H != W allowed)
+    through the inverse affine (zeros padding), differentiable wrt both arguments; this materialises [N,C,H,W], which the training step
+    itself never does (the renderer fuses it)."""
     from . import _lib as L
     if not image.is_cuda:
         raise L.SpairHipError("stn: tensors must live on the MI355X; there is no CPU path")
     N, C, H, W = image.shape
-    assert H == W and int(output_dims[0]) == int(output_dims[1]), "square images / glimpses only"
-    return _StnFn.apply(image, z_where, int(output_dims[0]), bool(inverse))
+    if inverse:
+        assert H == W, "square sprites only"
+        return _StnFn.apply(image, z_where, (int(output_dims[0]), int(output_dims[1])), True)
+    assert int(output_dims[0]) == int(output_dims[1]), "square glimpses only"
+    return _StnFn.apply(image, z_where, int(output_dims[0]), False)
 
 
 def _topology_conv_args(layer):
