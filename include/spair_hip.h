@@ -185,8 +185,8 @@ int spair_chain_stamps(const SpairDims* d, const void* workspace, unsigned long 
  * sampling interval (K4: modules.py:216-273 via models.py:387) among them, stamps per wavefront of the backward kernel (from offset 2048) */
 int spair_chain_stamp_layout(int* fwd_per_wavefront, int* fwd_glimpse_interval, int* bwd_per_wavefront);
 /* diagnostic: the kernels spair_forward / spair_backward choose for these dims, this workspace, SpairStep.flags `flags` and, for the
- * backward, whether an image gradient is requested (input_grad: spair_backward_x with grad_x).  Host arithmetic only (workspace is an address,
- * never read; nothing is launched).  Writes the first min(n, SPAIR_STEP_PLAN_INTS) of these ints to host `out`:
+ * backward, whether an image gradient is requested (input_grad: spair_backward_x with grad_x).  Host arithmetic only: of workspace only
+ * the address's 16-byte alignment is read (it must not be NULL; nothing is dereferenced, nothing is launched).  Writes the first min(n, SPAIR_STEP_PLAN_INTS) of these ints to host `out`:
  *   [0..7]   the renderer family of the forward and of the backward (SPAIR_RENDER_*), then 0/1 for: per-object records (render_prep), fp16
  *            sprites, bf16 d-logits, the fused per-cell chain kernels, the fused decoder forward; out[7] = 0;
  *   [8..11]  0/1 for: the helper stream, the decoder's data gradients in one launch, its two small weight gradients in one grouped launch,

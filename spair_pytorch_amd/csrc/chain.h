@@ -3,6 +3,26 @@
 
 enum ChainW { CW_BOX0, CW_BOX1, CW_BOXH, CW_ENC0, CW_ENC1, CW_ENC2, CW_Z0, CW_Z1, CW_ZH, CW_OBJ0, CW_OBJ1, CW_OBJ2, CW_COUNT };
 
+// The fragment packs of the chain's weights (k_prep mode 4 forward, mode 5 data gradient), per ChainW slot: the layer (a head's second layer
+// goes in at column NP of the same pack), the forward pack's nt column tiles x KT 1-KiB k-steps (ksplit / kpad0: where the input's second
+// part starts and where it is packed) and the data-gradient pack's ntt x KTt (ntt 0: none).  The box network's three slots also get a pack of
+// low parts (split-bf16 forward) the size of their forward pack.
+struct ChainPack { int lin, lin_head, nt, KT, ksplit, kpad0, ntt, KTt; };
+constexpr ChainPack CHAIN_PACK[CW_COUNT] = {
+    {LIN_BOX0, -1, 7, 11, 324, 352, 21, 4},
+    {LIN_BOX1, -1, 7, 4, SP_H, 128, 7, 4},
+    {LIN_BOXH1, LIN_BOXH0, 7, 4, SP_H, 128, 7, 4},
+    {LIN_ENC0, -1, 16, 25, 784, 800, 49, 8},
+    {LIN_ENC1, -1, 8, 8, 256, 256, 16, 4},
+    {LIN_ENC2, -1, 7, 4, 128, 128, 8, 4},
+    {LIN_Z0, -1, 7, 16, 324, 352, 30, 4},
+    {LIN_Z1, -1, 7, 4, SP_H, 128, 7, 4},
+    {LIN_ZH1, LIN_ZH0, 7, 4, SP_H, 128, 7, 4},
+    {LIN_OBJ0, -1, 7, 16, 324, 352, 30, 4},
+    {LIN_OBJ1, -1, 7, 4, SP_H, 128, 7, 4},
+    {LIN_OBJ2, -1, 1, 4, SP_H, 128, 0, 0},
+};
+
 struct ChainArgs {
     CellLayout L;
     CellBufs P;

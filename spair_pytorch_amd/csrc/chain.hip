@@ -29,6 +29,11 @@ constexpr int KX = 160, LD_XT = KX + CH_PAD;  // [pass | box | attr | depth] pad
 constexpr int KG = 800, LD_GL = KG + CH_PAD;  // glimpse padded to 25 k-steps
 constexpr int LD_H = 256 + CH_PAD;
 constexpr int LD_O = 112;
+// the packs the engine prepares (chain.h) for the inputs laid out above: 32 k per step
+static_assert(CHAIN_PACK[CW_BOX0].ksplit == F + CTX && CHAIN_PACK[CW_BOX0].kpad0 == KC && CHAIN_PACK[CW_BOX0].KT * 32 == KC, "box0 pack");
+static_assert(CHAIN_PACK[CW_Z0].ksplit == F + CTX && CHAIN_PACK[CW_Z0].kpad0 == KC && CHAIN_PACK[CW_Z0].KT * 32 == KC + KX, "z0 pack");
+static_assert(CHAIN_PACK[CW_OBJ0].ksplit == F + CTX && CHAIN_PACK[CW_OBJ0].kpad0 == KC && CHAIN_PACK[CW_OBJ0].KT * 32 == KC + KX, "obj0 pack");
+static_assert(CHAIN_PACK[CW_ENC0].ksplit == GLN && CHAIN_PACK[CW_ENC0].kpad0 == KG && CHAIN_PACK[CW_ENC0].KT * 32 == KG, "enc0 pack");
 
 // Workgroup barrier that orders LDS only.  __syncthreads() also drains every outstanding global access (s_waitcnt vmcnt(0)):
 // here that would stall each of the ~20 stages per wavefront on the acks of its activation stores and would force the weight

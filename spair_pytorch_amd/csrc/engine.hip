@@ -131,6 +131,109 @@ static int validate(const SpairDims& d) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// step plan
+// ---------------------------------------------------------------------------------------------
+// Which kernels the step runs: host arithmetic on the normalised dims, SpairStep.flags and input_grad, and on nothing else but the workspace
+// base's 16-byte alignment -- every buffer carve() hands out sits a multiple of 256 bytes past the base, so the base stands for the sprites,
+// records and d-logits the renderer's predicates test.  make_ctx plans the step, carve() the workspace (flags 0, no image gradient, an aligned
+// base: flags, the image gradient and a misaligned base only ever turn kernels off, so what any step plan reads the workspace has), and the
+// spair_step_plan diagnostics report it.  input_grad (spair_backward_x): the image gradient reads d act0 from HBM, so the stem's weight
+// gradient is not fused into conv_1's data gradient.
+// A rectangular image (Iw != I, or a rectangular padded frame) refuses every square-only kernel here, in the plan, whatever their _supported
+// predicates (most of which only see I) say: the fused chain, the records / matrix-core / second-generation renderer (render_plan), the
+// patch-resident strided convs, the stem fused into conv_1's data gradient, its bf16 weight-gradient kernel and the stem variants that read
+// the unpadded image.
+struct StepPlan {
+    bool use_chain;        // fused persistent per-cell kernels (bf16, reference network sizes)
+    bool use_dec_fused;    // the decoder forward as one activation-stationary kernel (bf16; SpairStep.flags bit 4 turns it off)
+    RenderPlan rp;         // the renderer's kernels and sprite / d-logit formats (render.h)
+    bool use_side;         // the helper stream (SpairStep.flags bit 2 turns it off)
+    // the backbone's kernels, per layer 1 .. PL.n_conv - 1 (the bf16 step's patch-resident ones: flags bit 5 turns them off)
+    int pw0;               // first layer of the fused trailing 1x1 stack (PL.n_conv: none)
+    ConvKernel conv_fwd[SP_MAX_CONV + 1], conv_dgrad[SP_MAX_CONV + 1];
+    bool gate_bits[SP_MAX_CONV + 1];   // a patch dgrad's gate: the sign bits the layer below wrote (else its activation)
+    bool stem_bits;        // the stem kernel writes act0's sign bits (misc_conv0_writes_mask)
+    StemWgrad stem_wgrad;
+    bool stem_unpadded;    // the stem reads the unpadded image itself (misc_conv0_reads_unpadded; square images)
+    // the bf16 step's decoder backward
+    bool dec_dgrad_fused;  // the three data gradients in one launch (dec_fused_bwd.hip; flags bit 6 turns it off)
+    bool dec_wgrad_grouped;    // the two small weight gradients in one grouped launch
+    bool dec_wgrad_late;   // the weight gradients issued behind the chain backward's launch (helper stream and fused chain)
+};
+
+// the renderer's objects: the rows' nbox, presence and depth (b null: the geometry alone, for the plan)
+static RenderGeom render_geom(const SpairDims& d, const CellLayout& L, const CellBufs* b) {
+    return {b ? b->nbox : nullptr, b ? b->rec + (L.REC - 1) : nullptr, b ? b->rec + (L.REC - 2) : nullptr, L.ld_rec, d.B, L.HW, d.I, d.P,
+            d.align_corners, d.Iw};
+}
+
+// The decoder's two small weight gradients as one grouped launch (decoder_small_wgrad_grouped): whole layers of at most 128 inputs, in tiles
+// of 128 output rows, operands addressed with 32-bit offsets
+static bool decoder_small_wgrad_grouped_supported(const ParamLayout& PL, const CellLayout& L) {
+    const LinSpec &l1 = PL.lin[LIN_DEC1], &l0 = PL.lin[LIN_DEC0];
+    return l1.in <= 128 && l0.in <= 128 && !(l1.out & 7) && !(l0.out & 7) && ceil_div(l1.out, 128) + ceil_div(l0.out, 128) <= SPAIR_TN_MAX_TILES &&
+           std::min(round_up(l1.in, 8), SP_DEC_H1) >= l1.in && std::min(round_up(l0.in, 8), L.ld_rec) >= l0.in &&
+           (long long)L.N * std::max(SP_DEC_H2, L.ld_rec) < (1ll << 31);
+}
+
+static StepPlan plan_step(const SpairDims& d, int flags, bool input_grad, const void* base) {
+    const CellLayout L = make_cell_layout(d);
+    const ParamLayout PL = make_param_layout(d);
+    StepPlan p = {};
+    const bool b16 = d.dtype == SPAIR_BF16;
+    const bool square = spair_dims_square(d);     // (the padded frame and the grid too)
+    const int per = d.P * d.P * (d.C + 1), ld_s = round_up(per, 8);
+    p.use_chain = square && chain_fwd_supported(d) && !(flags & 1) && !d.obj_conv;
+    const float* at = static_cast<const float*>(base);
+    p.rp = render_plan(d, render_geom(d, L, nullptr), ld_s, at, at, at);
+    p.use_dec_fused = p.rp.s16 /* it writes fp16 sprites */ && !(flags & 16) && PL.lin[LIN_DEC0].out == SP_DEC_H1 && PL.lin[LIN_DEC1].out == SP_DEC_H2 &&
+                      dec_fused_supported(d.A, per, L.ld_rec, L.N, ld_s);
+    p.use_side = !(flags & 4);
+    // backbone
+    const ConvSpec& c0 = PL.conv[0];
+    const bool grey4 = square && c0.cin == 1 && c0.k == 4 && c0.cout == 128;
+    const bool fuse_stem = b16 && grey4 && !(flags & 8) && !input_grad;
+    const bool patch = square && b16 && !(flags & 32);
+    p.stem_wgrad = b16 && grey4 ? STEM_WGRAD16 : STEM_GENERIC;
+    p.stem_unpadded = square && misc_conv0_reads_unpadded(d.B, c0.hin, d.C, c0.k, c0.cout);
+    p.stem_bits = square && misc_conv0_writes_mask(d.B, c0.hin, d.C, c0.k, c0.s, c0.cout, b16);
+    const int n = PL.n_conv;      // the trailing run of 1x1 layers pointwise.hip fuses: 128 channels in, 128 out except the last, 2 to 4 layers
+    p.pw0 = n;
+    for (int i = n - 1; b16 && i >= 1; --i) {
+        const ConvSpec& cs = PL.conv[i];
+        if (cs.k != 1 || cs.s != 1 || cs.cin != 128 || (i == n - 1 ? cs.cout > 128 : cs.cout != 128) || n - i > 4 || PL.conv[i - 1].cout != 128) break;
+        p.pw0 = i;
+    }
+    if (n - p.pw0 < 2) p.pw0 = n;
+    bool bits = p.stem_bits;     // whether the forward of the layer below leaves sign bits
+    for (int i = 1; i < n; ++i) {
+        const ConvSpec& cs = PL.conv[i];
+        if (i >= p.pw0) { p.conv_fwd[i] = p.conv_dgrad[i] = CONV_PW_STACK; continue; }
+        p.conv_fwd[i] = patch && conv_s2k4_patch_fwd16_supported(d.B, cs.hin, cs.hout, cs.cin, cs.cout, cs.k, cs.s) ? CONV_PATCH : CONV_GEMM;
+        if (cs.k == 1) p.conv_dgrad[i] = CONV_GEMM;
+        else if (patch && conv_s2k4_patch_dgrad16_supported(d.B, cs.hout, cs.hin, cs.cin, cs.cout, cs.k, cs.s)) {
+            p.conv_dgrad[i] = CONV_PATCH;
+            p.gate_bits[i] = bits;
+            if (i == 1 && fuse_stem &&
+                conv_s2k4_patch_dgrad16_stem_supported(d.B, cs.hout, cs.hin, cs.cin, cs.cout, cs.k, cs.s, c0.hin, c0.s, SPAIR_TN_PART_FLOATS))
+                p.stem_wgrad = STEM_PATCH;
+        } else if (b16 && cs.hin % cs.s == 0 && cs.win % cs.s == 0 && cs.s * cs.s <= 4) {     // (every parity class the same size)
+            p.conv_dgrad[i] = CONV_GEMM;
+            // conv_1's classes in one launch (dgrad_classes16): rows of class (0, 0), one class per blockIdx.z
+            const int M = d.B * ceil_div(cs.hin, cs.s) * ceil_div(cs.win, cs.s);
+            if (i == 1 && fuse_stem && spair_nt16_stem_fusable(M, cs.cin, cs.s * cs.s, c0.hin, c0.s, SPAIR_TN_PART_FLOATS)) p.stem_wgrad = STEM_GEMM;
+        } else p.conv_dgrad[i] = CONV_PER_CLASS;
+        bits = p.conv_fwd[i] == CONV_PATCH;
+    }
+    // the bf16 step's MLP decoder backward
+    const bool dec16 = b16 && !PL.oc_n;
+    p.dec_dgrad_fused = dec16 && !(flags & 64) && dec_fused_bwd_supported(PL.lin[LIN_DEC0].in, per, L.N, ld_s, ld_s, L.ld_rec);
+    p.dec_wgrad_grouped = dec16 && decoder_small_wgrad_grouped_supported(PL, L);
+    p.dec_wgrad_late = dec16 && p.use_side && p.use_chain;
+    return p;
+}
+
+// ---------------------------------------------------------------------------------------------
 // workspace
 // ---------------------------------------------------------------------------------------------
 struct Ws {
@@ -179,11 +282,14 @@ struct Carver {
     void* take_bytes(size_t n) { return take<char>(n); }
 };
 
+// The buffers of a step on this workspace, in a fixed order.  An optional buffer is taken where the workspace's plan (flags 0, no image
+// gradient, aligned: see plan_step) reads it, so no step plan on the workspace reaches one that is left null.
 static Ws carve(const SpairDims& d, void* base) {
     Ws w;
     memset(&w, 0, sizeof(w));
     const CellLayout L = make_cell_layout(d);
     const ParamLayout PL = make_param_layout(d);
+    const StepPlan p = plan_step(d, 0, false, nullptr);
     Carver c{reinterpret_cast<char*>(base), 0};
     const size_t es = d.dtype == SPAIR_BF16 ? 2 : 4;
     const size_t N = (size_t)L.N;
@@ -213,19 +319,15 @@ static Ws carve(const SpairDims& d, void* base) {
     }
     w.bias_boxh = c.take<float>(L.NP + 8);
     w.bias_zh = c.take<float>(L.NP + 8);
-    if (chain_fwd_supported(d)) {
-        const int nt[CW_COUNT] = {7, 7, 7, 16, 8, 7, 7, 7, 7, 7, 7, 1};
-        const int kt[CW_COUNT] = {11, 4, 4, 25, 8, 4, 16, 4, 4, 16, 4, 4};
-        for (int i = 0; i < CW_COUNT; ++i) w.chain_w[i] = c.take_bytes((size_t)nt[i] * kt[i] * 1024);
-        for (int i = 0; i < 3; ++i) w.chain_wlo[i] = c.take_bytes((size_t)nt[i] * kt[i] * 1024);
-        const int ntb[CW_COUNT] = {21, 7, 7, 49, 16, 8, 30, 7, 7, 30, 7, 0};
-        const int ktb[CW_COUNT] = {4, 4, 4, 8, 4, 4, 4, 4, 4, 4, 4, 0};
-        for (int i = 0; i < CW_COUNT; ++i) w.chain_wt[i] = ntb[i] ? c.take_bytes((size_t)ntb[i] * ktb[i] * 1024) : nullptr;
+    if (p.use_chain) {
+        for (int i = 0; i < CW_COUNT; ++i) w.chain_w[i] = c.take_bytes((size_t)CHAIN_PACK[i].nt * CHAIN_PACK[i].KT * 1024);
+        for (int i = 0; i < 3; ++i) w.chain_wlo[i] = c.take_bytes((size_t)CHAIN_PACK[i].nt * CHAIN_PACK[i].KT * 1024);
+        for (int i = 0; i < CW_COUNT; ++i)
+            w.chain_wt[i] = CHAIN_PACK[i].ntt ? c.take_bytes((size_t)CHAIN_PACK[i].ntt * CHAIN_PACK[i].KTt * 1024) : nullptr;
     }
-    w.dec_stream = d.dtype == SPAIR_BF16 ? c.take_bytes(dec_fused_stream_bytes(d.P * d.P * (d.C + 1))) : nullptr;
+    w.dec_stream = p.use_dec_fused ? c.take_bytes(dec_fused_stream_bytes(d.P * d.P * (d.C + 1))) : nullptr;
     // backbone
     const int Ip = d.I + d.pad_pre + d.pad_post, Ipw = d.Iw + d.pad_pre + d.pad_post_w;
-    const bool square = spair_dims_square(d);
     w.xpad = c.take<float>((size_t)d.B * Ip * Ipw * d.C);
     for (int i = 0; i < d.n_conv; ++i) {
         const ConvSpec& cs = PL.conv[i];
@@ -233,16 +335,9 @@ static Ws carve(const SpairDims& d, void* base) {
         w.act[i] = reinterpret_cast<float*>(c.take_bytes(n * es));      // NHWC, bf16 in bf16 mode
         w.dact[i] = reinterpret_cast<float*>(c.take_bytes(n * es));
     }
-    {
-        const ConvSpec& c0 = PL.conv[0];
-        w.act0_bits = square && misc_conv0_writes_mask(d.B, c0.hin, d.C, c0.k, c0.s, c0.cout, d.dtype == SPAIR_BF16)
-                          ? c.take<unsigned char>((size_t)d.B * c0.hout * c0.hout * 16) : nullptr;
-    }
-    for (int i = 1; i < d.n_conv; ++i) {
-        const ConvSpec& cs = PL.conv[i];
-        w.act_bits[i] = (square && d.dtype == SPAIR_BF16 && cs.k == 4 && cs.s == 2 && cs.cin == 128 && cs.cout == 128)
-                            ? c.take<unsigned char>((size_t)d.B * cs.hout * cs.hout * 16) : nullptr;
-    }
+    if (p.stem_bits) w.act0_bits = c.take<unsigned char>((size_t)d.B * PL.conv[0].hout * PL.conv[0].hout * 16);
+    for (int i = 1; i < d.n_conv; ++i)
+        if (p.conv_fwd[i] == CONV_PATCH) w.act_bits[i] = c.take<unsigned char>((size_t)d.B * PL.conv[i].hout * PL.conv[i].hout * 16);
     w.ld_feat = round_up(d.F, 8);
     w.feat = c.take<float>(N * w.ld_feat);
     w.dfeat = c.take<float>(N * w.ld_feat);
@@ -265,16 +360,17 @@ static Ws carve(const SpairDims& d, void* base) {
     w.ld_s = round_up(d.P * d.P * (d.C + 1), 8);
     w.Za = c.take<float>(N * L.ld_rec);
     b.Za = w.Za;
-    b.gxy = chain_fwd_supported(d) ? c.take<unsigned int>(N * L.ld_gl) : nullptr;
-    const int nbands = chain_fwd_supported(d) ? chain_bands(d) : 1;
-    b.mbits = chain_fwd_supported(d) ? c.take<unsigned long long>((size_t)d.B * nbands * (3 * d.G - 2) * 66 * 4) : nullptr;
+    b.gxy = p.use_chain ? c.take<unsigned int>(N * L.ld_gl) : nullptr;
+    const int nbands = p.use_chain ? chain_bands(d) : 1;
+    b.mbits = p.use_chain ? c.take<unsigned long long>((size_t)d.B * nbands * (3 * d.G - 2) * 66 * 4) : nullptr;
     w.Hd1 = reinterpret_cast<float*>(c.take_bytes(N * SP_DEC_H1 * es)); w.Hd2 = reinterpret_cast<float*>(c.take_bytes(N * SP_DEC_H2 * es));
     w.S = c.take<float>(N * w.ld_s);
-    // (fp32 outside render_16bit; the bf16 step's decoder backward reads the colour renderer's through the bf16 copy dLog16)
-    w.dLog = reinterpret_cast<float*>(c.take_bytes(N * w.ld_s * (render_16bit(d) ? 2 : 4)));
-    w.dLog16 = (d.dtype == SPAIR_BF16 && d.C != 1) ? c.take_bytes(N * w.ld_s * 2) : nullptr;
+    // (the bf16 step's MLP decoder backward reads fp32 d-logits through the bf16 copy dLog16)
+    w.dLog = reinterpret_cast<float*>(c.take_bytes(N * w.ld_s * (p.rp.g16 ? 2 : 4)));
+    const bool bf16 = d.dtype == SPAIR_BF16;
+    w.dLog16 = bf16 && !PL.oc_n && !p.rp.g16 ? c.take_bytes(N * w.ld_s * 2) : nullptr;
     w.dHd2 = reinterpret_cast<float*>(c.take_bytes(N * SP_DEC_H2 * es)); w.dHd1 = reinterpret_cast<float*>(c.take_bytes(N * SP_DEC_H1 * es));
-    w.Za16 = c.take_bytes(N * L.ld_rec * 2); w.dfeat16 = c.take_bytes(N * w.ld_feat * 2);
+    if (bf16) { w.Za16 = c.take_bytes(N * L.ld_rec * 2); w.dfeat16 = c.take_bytes(N * w.ld_feat * 2); }
     b.Za16 = w.Za16; b.dfeat16 = w.dfeat16;
     w.tn_part = reinterpret_cast<float*>(c.take_bytes((size_t)SPAIR_TN_PART_FLOATS * 4));
     w.tn_part2 = reinterpret_cast<float*>(c.take_bytes((size_t)SPAIR_TN_PART_FLOATS * 4));
@@ -392,7 +488,7 @@ extern "C" int spair_param_info(const SpairDims* d, int idx, char* name, int nam
 // ---------------------------------------------------------------------------------------------
 // step context
 // ---------------------------------------------------------------------------------------------
-struct Ctx {
+struct Ctx : StepPlan {     // the step's plan (plan_step), its buffers and arguments
     SpairDims d;
     SpairStep st;
     CellLayout L;
@@ -403,21 +499,7 @@ struct Ctx {
     const float* x;
     hipStream_t s;
     int T;                 // number of wavefront diagonals
-    int use_chain;         // fused persistent per-cell kernels (bf16, reference network sizes)
-    int use_dec_fused;     // the decoder forward as one activation-stationary kernel (bf16; SpairStep.flags bit 4 turns it off)
     RenderGeom rg;         // the renderer's objects: the rows' nbox, presence and depth
-    RenderPlan rp;         // the renderer's kernels and sprite / d-logit formats (render.h)
-    bool use_side;         // the helper stream (SpairStep.flags bit 2 turns it off)
-    // the backbone's kernels, per layer 1 .. PL.n_conv - 1 (the bf16 step's patch-resident ones: flags bit 5 turns them off)
-    int pw0;               // first layer of the fused trailing 1x1 stack (PL.n_conv: none)
-    ConvKernel conv_fwd[SP_MAX_CONV + 1], conv_dgrad[SP_MAX_CONV + 1];
-    const unsigned char* dgrad_bits[SP_MAX_CONV + 1];      // a patch dgrad's gate: the sign bits the layer below left (null: its activation)
-    StemWgrad stem_wgrad;
-    bool stem_unpadded;    // the stem reads the unpadded image itself (misc_conv0_reads_unpadded; square images)
-    // the bf16 step's decoder backward
-    bool dec_dgrad_fused;  // the three data gradients in one launch (dec_fused_bwd.hip; flags bit 6 turns it off)
-    bool dec_wgrad_grouped;    // the two small weight gradients in one grouped launch
-    bool dec_wgrad_late;   // the weight gradients issued behind the chain backward's launch (helper stream and fused chain)
     float* tn_part;        // split-K scratch of c.s: w.tn_part, w.tn_part2 on the helper stream (OnHelper)
     std::vector<int> dstart;
 };
@@ -609,50 +691,23 @@ static int prep_weights(Ctx& c, bool need_dgrad, int part) {
         }
     }
     if (part == 1 && c.use_chain) {
-        auto pack = [&](int cw, int lin_id, int KT, int ksplit, int kpad0, int n_off) {
-            const LinSpec& l = c.PL.lin[lin_id];
-            PrepEntry e;
-            memset(&e, 0, sizeof(e));
-            e.src = c.params + l.w; e.dst = c.w.chain_w[cw]; e.rows = l.out; e.cols = l.in; e.mode = 4; e.bf16 = 1;
-            e.KT = KT; e.ksplit = ksplit; e.kpad0 = kpad0; e.n_off = n_off;
-            es.push_back(e);
-        };
-        const int fc = c.L.F + c.L.CTX;   // 324
-        auto pack_lo = [&](int cw, int lin_id, int KT, int ksplit, int kpad0, int n_off) {      // same pack, low parts (bf16 = 2)
-            pack(cw, lin_id, KT, ksplit, kpad0, n_off);
-            es.back().dst = c.w.chain_wlo[cw]; es.back().bf16 = 2;
-        };
-        pack_lo(CW_BOX0, LIN_BOX0, 11, fc, 352, 0);
-        pack_lo(CW_BOX1, LIN_BOX1, 4, SP_H, 128, 0);
-        pack_lo(CW_BOXH, LIN_BOXH1, 4, SP_H, 128, 0); pack_lo(CW_BOXH, LIN_BOXH0, 4, SP_H, 128, c.L.NP);
-        pack(CW_BOX0, LIN_BOX0, 11, fc, 352, 0);
-        pack(CW_BOX1, LIN_BOX1, 4, SP_H, 128, 0);
-        pack(CW_BOXH, LIN_BOXH1, 4, SP_H, 128, 0); pack(CW_BOXH, LIN_BOXH0, 4, SP_H, 128, c.L.NP);
-        pack(CW_ENC0, LIN_ENC0, 25, 784, 800, 0);
-        pack(CW_ENC1, LIN_ENC1, 8, 256, 256, 0);
-        pack(CW_ENC2, LIN_ENC2, 4, 128, 128, 0);
-        pack(CW_Z0, LIN_Z0, 16, fc, 352, 0);
-        pack(CW_Z1, LIN_Z1, 4, SP_H, 128, 0);
-        pack(CW_ZH, LIN_ZH1, 4, SP_H, 128, 0); pack(CW_ZH, LIN_ZH0, 4, SP_H, 128, c.L.NP);
-        pack(CW_OBJ0, LIN_OBJ0, 16, fc, 352, 0);
-        pack(CW_OBJ1, LIN_OBJ1, 4, SP_H, 128, 0);
-        pack(CW_OBJ2, LIN_OBJ2, 4, SP_H, 128, 0);
-        if (need_dgrad) {
-            auto packt = [&](int cw, int lin_id, int KT, int k_off) {
-                const LinSpec& l = c.PL.lin[lin_id];
+        // the fused chain's fragment packs (chain.h): the box network's low parts, every slot's forward pack, then the data-gradient packs
+        auto pack = [&](void* const* dst, int cw, int mode, int bf16) {
+            const ChainPack& k = CHAIN_PACK[cw];
+            for (int head = 0; head < (k.lin_head >= 0 ? 2 : 1); ++head) {
+                const LinSpec& l = c.PL.lin[head ? k.lin_head : k.lin];
                 PrepEntry e;
                 memset(&e, 0, sizeof(e));
-                e.src = c.params + l.w; e.dst = c.w.chain_wt[cw]; e.rows = l.out; e.cols = l.in; e.mode = 5; e.bf16 = 1;
-                e.KT = KT; e.n_off = k_off;
+                e.src = c.params + l.w; e.dst = dst[cw]; e.rows = l.out; e.cols = l.in; e.mode = mode; e.bf16 = bf16;
+                e.KT = mode == 4 ? k.KT : k.KTt; e.n_off = head ? c.L.NP : 0;
+                if (mode == 4) { e.ksplit = k.ksplit; e.kpad0 = k.kpad0; }
                 es.push_back(e);
-            };
-            packt(CW_BOX0, LIN_BOX0, 4, 0); packt(CW_BOX1, LIN_BOX1, 4, 0);
-            packt(CW_BOXH, LIN_BOXH1, 4, 0); packt(CW_BOXH, LIN_BOXH0, 4, c.L.NP);
-            packt(CW_ENC0, LIN_ENC0, 8, 0); packt(CW_ENC1, LIN_ENC1, 4, 0); packt(CW_ENC2, LIN_ENC2, 4, 0);
-            packt(CW_Z0, LIN_Z0, 4, 0); packt(CW_Z1, LIN_Z1, 4, 0);
-            packt(CW_ZH, LIN_ZH1, 4, 0); packt(CW_ZH, LIN_ZH0, 4, c.L.NP);
-            packt(CW_OBJ0, LIN_OBJ0, 4, 0); packt(CW_OBJ1, LIN_OBJ1, 4, 0);
-        }
+            }
+        };
+        for (int cw = 0; cw < 3; ++cw) pack(c.w.chain_wlo, cw, 4, 2);
+        for (int cw = 0; cw < CW_COUNT; ++cw) pack(c.w.chain_w, cw, 4, 1);
+        for (int cw = 0; need_dgrad && cw < CW_COUNT; ++cw)
+            if (CHAIN_PACK[cw].ntt) pack(c.w.chain_wt, cw, 5, 1);
     }
     if (part == 1 && c.use_dec_fused)
         TRY(dec_fused_pack(c.params + c.PL.lin[LIN_DEC0].w, c.params + c.PL.lin[LIN_DEC1].w, c.params + c.PL.lin[LIN_DEC2].w, c.d.A,
@@ -706,73 +761,6 @@ static GemmNT dgrad_classes16(const Ctx& c, int i) {
     return g;
 }
 
-// The decoder's two small weight gradients as one grouped launch (decoder_small_wgrad_grouped): whole layers of at most 128 inputs, in tiles
-// of 128 output rows, operands addressed with 32-bit offsets
-static bool decoder_small_wgrad_grouped_supported(const Ctx& c) {
-    const LinSpec &l1 = c.PL.lin[LIN_DEC1], &l0 = c.PL.lin[LIN_DEC0];
-    return l1.in <= 128 && l0.in <= 128 && !(l1.out & 7) && !(l0.out & 7) && ceil_div(l1.out, 128) + ceil_div(l0.out, 128) <= SPAIR_TN_MAX_TILES &&
-           std::min(round_up(l1.in, 8), SP_DEC_H1) >= l1.in && std::min(round_up(l0.in, 8), c.L.ld_rec) >= l0.in &&
-           (long long)c.L.N * std::max(SP_DEC_H2, c.L.ld_rec) < (1ll << 31);
-}
-
-// ---- step plan -----------------------------------------------------------------------------------------
-// Which kernels the step runs (host arithmetic on c.d, c.L, c.PL and c.w only): make_ctx and the spair_step_plan diagnostics.  input_grad
-// (spair_backward_x): the image gradient reads d act0 from HBM, so the stem's weight gradient is not fused into conv_1's data gradient.
-// A rectangular image (Iw != I) refuses every square-only kernel here, in the plan, whatever their _supported predicates (most of which only
-// see I) say: the fused chain, the records / matrix-core / second-generation renderer (render_plan), the patch-resident strided convs, the
-// stem fused into conv_1's data gradient, its bf16 weight-gradient kernel and the stem variants that read the unpadded image.
-static void plan_step(Ctx& c, int flags, bool input_grad) {
-    const SpairDims& d = c.d;
-    const bool b16 = d.dtype == SPAIR_BF16;
-    const bool square = d.Iw == d.I;
-    c.use_chain = square && chain_fwd_supported(d) && !(flags & 1) && !d.obj_conv;
-    c.rg = {c.w.cb.nbox, c.w.cb.rec + (c.L.REC - 1), c.w.cb.rec + (c.L.REC - 2), c.L.ld_rec, d.B, c.L.HW, d.I, d.P, d.align_corners, d.Iw};
-    c.rp = render_plan(d, c.rg, c.w.ld_s, c.w.S, c.w.rrec, c.w.dLog);
-    c.use_dec_fused = c.rp.s16 /* it writes fp16 sprites */ && !(flags & 16) && c.PL.lin[LIN_DEC0].out == SP_DEC_H1 && c.PL.lin[LIN_DEC1].out == SP_DEC_H2 &&
-                      dec_fused_supported(d.A, d.P * d.P * (d.C + 1), c.L.ld_rec, c.L.N, c.w.ld_s);
-    c.use_side = !(flags & 4);
-    // backbone
-    const ConvSpec& c0 = c.PL.conv[0];
-    const bool grey4 = square && c0.cin == 1 && c0.k == 4 && c0.cout == 128;
-    const bool fuse_stem = b16 && grey4 && !(flags & 8) && !input_grad;
-    const bool patch = square && b16 && !(flags & 32);
-    c.stem_wgrad = b16 && grey4 ? STEM_WGRAD16 : STEM_GENERIC;
-    c.stem_unpadded = square && misc_conv0_reads_unpadded(d.B, c0.hin, d.C, c0.k, c0.cout);
-    const int n = c.PL.n_conv;      // the trailing run of 1x1 layers pointwise.hip fuses: 128 channels in, 128 out except the last, 2 to 4 layers
-    c.pw0 = n;
-    for (int i = n - 1; b16 && i >= 1; --i) {
-        const ConvSpec& cs = c.PL.conv[i];
-        if (cs.k != 1 || cs.s != 1 || cs.cin != 128 || (i == n - 1 ? cs.cout > 128 : cs.cout != 128) || n - i > 4 || c.PL.conv[i - 1].cout != 128) break;
-        c.pw0 = i;
-    }
-    if (n - c.pw0 < 2) c.pw0 = n;
-    const unsigned char* bits = c.w.act0_bits;     // what the forward of the layer below leaves: the stem kernel's sign bits (misc_conv0_writes_mask)
-    for (int i = 1; i < n; ++i) {
-        const ConvSpec& cs = c.PL.conv[i];
-        c.dgrad_bits[i] = nullptr;
-        if (i >= c.pw0) { c.conv_fwd[i] = c.conv_dgrad[i] = CONV_PW_STACK; continue; }
-        c.conv_fwd[i] = patch && conv_s2k4_patch_fwd16_supported(d.B, cs.hin, cs.hout, cs.cin, cs.cout, cs.k, cs.s) ? CONV_PATCH : CONV_GEMM;
-        if (cs.k == 1) c.conv_dgrad[i] = CONV_GEMM;
-        else if (patch && conv_s2k4_patch_dgrad16_supported(d.B, cs.hout, cs.hin, cs.cin, cs.cout, cs.k, cs.s)) {
-            c.conv_dgrad[i] = CONV_PATCH;
-            c.dgrad_bits[i] = bits;
-            if (i == 1 && fuse_stem &&
-                conv_s2k4_patch_dgrad16_stem_supported(d.B, cs.hout, cs.hin, cs.cin, cs.cout, cs.k, cs.s, c0.hin, c0.s, SPAIR_TN_PART_FLOATS))
-                c.stem_wgrad = STEM_PATCH;
-        } else if (b16 && cs.hin % cs.s == 0 && cs.win % cs.s == 0 && cs.s * cs.s <= 4) {     // (every parity class the same size)
-            c.conv_dgrad[i] = CONV_GEMM;
-            if (i == 1 && fuse_stem && spair_nt16_stem_fusable(dgrad_classes16(c, 1), SPAIR_TN_PART_FLOATS)) c.stem_wgrad = STEM_GEMM;
-        } else c.conv_dgrad[i] = CONV_PER_CLASS;
-        bits = c.conv_fwd[i] == CONV_PATCH ? c.w.act_bits[i] : nullptr;
-    }
-    // the bf16 step's MLP decoder backward
-    const bool dec16 = b16 && !c.PL.oc_n;
-    const int per = d.P * d.P * (d.C + 1);
-    c.dec_dgrad_fused = dec16 && !(flags & 64) && dec_fused_bwd_supported(c.PL.lin[LIN_DEC0].in, per, c.L.N, c.w.ld_s, round_up(per, 8), c.L.ld_rec);
-    c.dec_wgrad_grouped = dec16 && decoder_small_wgrad_grouped_supported(c);
-    c.dec_wgrad_late = dec16 && c.use_side && c.use_chain;
-}
-
 static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
                     const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace, void* stream, bool input_grad = false) {
     if (!d || !st || !params || !x || !workspace) return SPAIR_ERR_SHAPE;
@@ -795,7 +783,8 @@ static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const float
     c.w.cb.edge = params + c.PL.edge;
     c.w.cb.eps_box = eps_box; c.w.cb.eps_attr = eps_attr; c.w.cb.eps_depth = eps_depth; c.w.cb.u_pres = u_pres;
     fill_diag(c);
-    plan_step(c, st->flags, input_grad);
+    static_cast<StepPlan&>(c) = plan_step(*d, st->flags, input_grad, workspace);
+    c.rg = render_geom(*d, c.L, &c.w.cb);
     return SPAIR_OK;
 }
 
@@ -905,7 +894,7 @@ static int backbone_bwd16(Ctx& c, float* grads) {
             const void* wd4[4] = {c.w.conv_wd[i][0], c.w.conv_wd[i][1], c.w.conv_wd[i][2], c.w.conv_wd[i][3]};
             TRY(conv_s2k4_patch_dgrad16(dout, wd4, in, c.w.dact[i - 1], d.B, cs.hout, cs.hin, cs.cin, cs.cout, cs.k, cs.s, stem ? c.w.xpad : nullptr,
                                         c0.hin, c0.s, stem ? c.w.tn_part : nullptr, SPAIR_TN_PART_FLOATS, grads + c0.w, grads + c0.b, c.s,
-                                        c.dgrad_bits[i]));
+                                        !c.gate_bits[i] ? nullptr : i == 1 ? c.w.act0_bits : c.w.act_bits[i - 1]));
         } else if (c.conv_dgrad[i] == CONV_GEMM) {
             // all output-parity classes in one launch, blockIdx.z = class (4 launches of 1.1 rounds of resident blocks each ran as 2 rounds:
             // conv2's data-gradient took 0.37 ms for 34 GFLOP); conv_1 may take the stem's weight gradient from the tile in LDS
@@ -1359,7 +1348,7 @@ static int decoder_small_wgrad_grouped(Ctx& c, float* grads, long long N) {
             t.M = round_up(ms, 8); t.N = std::min(round_up(l.in, 8), ldi); t.Mstore = ms; t.Nstore = l.in; t.m_skip = 0; t.n_skip = 0;
         }
     };
-    if (!decoder_small_wgrad_grouped_supported(c)) return SPAIR_ERR_UNSUPPORTED;
+    if (!decoder_small_wgrad_grouped_supported(c.PL, c.L)) return SPAIR_ERR_UNSUPPORTED;
     add(l1, c.w.dHd2, SP_DEC_H2, c.w.Hd1, SP_DEC_H1);
     add(l0, c.w.dHd1, SP_DEC_H1, c.w.Za16, c.L.ld_rec);
     g.ngroup = nt; g.R = (int)N;
@@ -1645,20 +1634,18 @@ extern "C" int spair_chain_stamps(const SpairDims* d0, const void* workspace, un
 static_assert(SPAIR_RENDER_MMA == RENDER_MMA && SPAIR_RENDER_GEN2 == RENDER_GEN2 && SPAIR_RENDER_GEN1 == RENDER_GEN1 &&
               SPAIR_RENDER_COLOUR == RENDER_COLOUR, "include/spair_hip.h names the RenderFamily values");
 static_assert(SPAIR_STEP_PLAN_INTS == 14 + 3 * SP_MAX_CONV, "include/spair_hip.h lays out spair_step_plan_n");
-// diagnostic: the kernel plan make_ctx computes for these dims, workspace, SpairStep.flags and input gradient (host only: nothing launched,
-// nothing read)
+// diagnostic: the kernel plan make_ctx computes for these dims, workspace alignment, SpairStep.flags and input gradient (host only: nothing
+// launched, nothing read)
 extern "C" int spair_step_plan_n(const SpairDims* d0, const void* workspace, int flags, int input_grad, int* out, int n) {
     if (!d0 || !workspace || !out) return SPAIR_ERR_SHAPE;
     const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
     TRY(validate(*d));
-    Ctx c;
-    c.d = *d; c.L = make_cell_layout(*d); c.PL = make_param_layout(*d); c.w = carve(*d, const_cast<void*>(workspace));
-    plan_step(c, flags, input_grad != 0);
-    int v[SPAIR_STEP_PLAN_INTS] = {c.rp.fwd, c.rp.bwd, c.rp.rec, c.rp.s16, c.rp.g16, c.use_chain, c.use_dec_fused, 0,
-                                   c.use_side, c.dec_dgrad_fused, c.dec_wgrad_grouped, c.dec_wgrad_late, c.pw0, c.stem_wgrad};
+    const StepPlan p = plan_step(*d, flags, input_grad != 0, workspace);
+    int v[SPAIR_STEP_PLAN_INTS] = {p.rp.fwd, p.rp.bwd, p.rp.rec, p.rp.s16, p.rp.g16, p.use_chain, p.use_dec_fused, 0,
+                                   p.use_side, p.dec_dgrad_fused, p.dec_wgrad_grouped, p.dec_wgrad_late, p.pw0, p.stem_wgrad};
     for (int i = 1; i <= SP_MAX_CONV; ++i) {      // per layer: forward, data gradient, gate bits (-1 past conv_out)
-        const bool on = i < c.PL.n_conv;
-        v[13 + i] = on ? c.conv_fwd[i] : -1; v[21 + i] = on ? c.conv_dgrad[i] : -1; v[29 + i] = on ? c.dgrad_bits[i] != nullptr : -1;
+        const bool on = i <= d->n_conv;
+        v[13 + i] = on ? p.conv_fwd[i] : -1; v[21 + i] = on ? p.conv_dgrad[i] : -1; v[29 + i] = on ? p.gate_bits[i] : -1;
     }
     for (int i = 0; i < std::min(n, SPAIR_STEP_PLAN_INTS); ++i) out[i] = v[i];
     return SPAIR_OK;
@@ -1682,7 +1669,8 @@ extern "C" int spair_chain_sync_status(const SpairDims* d0, const void* workspac
 extern "C" int spair_chain_stamp_wavefronts(const SpairDims* d0) {
     if (!d0) return SPAIR_ERR_SHAPE;
     const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
-    const int nb = chain_fwd_supported(*d) ? chain_bands(*d) : 1;
+    TRY(validate(*d));
+    const int nb = plan_step(*d, 0, false, nullptr).use_chain ? chain_bands(*d) : 1;
     const int hb = (d->G + nb - 1) / nb;
     return 2 * (hb - 1) + d->G;
 }

@@ -28,7 +28,9 @@ struct GemmNT {
     // store; per-workgroup partials go to stem_part (capacity in floats), their sum is added to stem_dw [128][16] / stem_db [128].
     const float* stem_xp; float* stem_part; long long stem_part_cap; float* stem_dw; float* stem_db; int stem_hin, stem_s;
 };
-bool spair_nt16_stem_fusable(const GemmNT& g, long long part_cap);
+// whether conv_1's data gradient (M rows per class, N channels, nz parity classes; stem_hin / stem_s as above) can take the stem's weight
+// gradient with part_cap floats of partials (the launch must also be row-mapped with a bf16 C)
+bool spair_nt16_stem_fusable(int M, int N, int nz, int stem_hin, int stem_s, long long part_cap);
 #define SPAIR_TN_MAX_TILES 40
 struct GemmTN {
     const float* A; int lda;

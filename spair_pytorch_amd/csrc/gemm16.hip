@@ -547,10 +547,9 @@ int spair_stem_fused_reduce(float* part, int nblk, float* dw, float* db, hipStre
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
-bool spair_nt16_stem_fusable(const GemmNT& g, long long part_cap) {
-    const long long tiles = (long long)ceil_div(g.M, 128) * (g.nz > 1 ? g.nz : 1);
-    return g.N == 128 && g.use_cmap && g.c_bf16 && (g.stem_hin % 2) == 0 && (g.stem_s % 2) == 0 &&
-           (tiles + 64) * STEM_PART_FLOATS <= part_cap;
+bool spair_nt16_stem_fusable(int M, int N, int nz, int stem_hin, int stem_s, long long part_cap) {
+    const long long tiles = (long long)ceil_div(M, 128) * (nz > 1 ? nz : 1);
+    return N == 128 && (stem_hin % 2) == 0 && (stem_s % 2) == 0 && (tiles + 64) * STEM_PART_FLOATS <= part_cap;
 }
 
 int spair_gemm_nt16_impl(const GemmNT& g_in, bool conv, hipStream_t s) {
@@ -595,7 +594,8 @@ int spair_gemm_nt16_impl(const GemmNT& g_in, bool conv, hipStream_t s) {
 #define NT16_LAUNCH(AC, C16, ST)                                                                                 \
     do { if (bk == 32) NT16_LAUNCH_BK(AC, C16, ST, 32); else NT16_LAUNCH_BK(AC, C16, ST, 64); } while (0)
     if (g.stem_part) {   // conv_1's data gradient with the stem's weight gradient taken in the epilogue
-        if (!conv || !g.stem_xp || !g.stem_dw || !spair_nt16_stem_fusable(g, g.stem_part_cap)) return SPAIR_ERR_UNSUPPORTED;
+        if (!conv || !g.stem_xp || !g.stem_dw || !g.use_cmap || !g.c_bf16 ||
+            !spair_nt16_stem_fusable(g.M, g.N, g.nz, g.stem_hin, g.stem_s, g.stem_part_cap)) return SPAIR_ERR_UNSUPPORTED;
         NT16_LAUNCH(true, true, true);
         SPAIR_CHECK_LAUNCH();
         return spair_stem_fused_reduce(g.stem_part, ceil_div(g.M, 128) * (g.nz > 1 ? g.nz : 1), g.stem_dw, g.stem_db, s);
