@@ -213,6 +213,32 @@ int spair_chain_stamp_layout(int* fwd_per_wavefront, int* fwd_glimpse_interval, 
 int spair_step_plan_n(const SpairDims* d, const void* workspace, int flags, int input_grad, int* out, int n);
 /* the first 8 ints of spair_step_plan_n without an image gradient */
 int spair_step_plan(const SpairDims* d, const void* workspace, int flags, int* out);
+/* diagnostic: where the buffer `name` of a step's workspace lies, for the step plan of (flags, input_grad) as spair_step_plan_n takes them.
+ * Host arithmetic only, as spair_step_plan_n (workspace is an address, never dereferenced).  Writes to host `out`: [0] byte offset from
+ * workspace, [1] rows, [2] meaningful columns, [3] leading dimension in elements, [4] element type (0 fp32, 1 bf16, 2 fp16) as that plan
+ * writes the buffer, [5] 1 if that plan's training step (forward + backward) writes it, else 0.  No buffer is aliased: the regions never
+ * overlap, and every one keeps what the last step left until the next step on the workspace.  Returns SPAIR_ERR_SHAPE for an unknown name,
+ * SPAIR_ERR_UNSUPPORTED for a buffer these dims do not allocate.  Names (rows r = cprime * B + b in dependency-wavefront order, N = B Gh Gw):
+ *   per-cell rows, N each -- bf16 from the fused chain, fp32 from the per-wavefront launches (SpairStep.flags bit 0), except the head outputs
+ *   Ob, Oe, Oz, Oo (fp32 always) and dGl (fp32):
+ *     Xb [features | context], Hb1, Hb2 (box network hidden), Ob [pass NP | lat 8]; glimpse, He1, He2, Oe [mean A | logstd A] (encoder);
+ *     Xz [features | context | pass | box 4 | attr A], Hz1, Hz2, Oz [pass NP | lat 2]; Xo [Xz's columns | depth], Ho1, Ho2, Oo [logit];
+ *     dXb dHb1 dHb2 dOb dGl dHe1 dHe2 dOe dXz dHz1 dHz2 dOz dXo dHo1 dHo2 dOo: their gradients (the fused chain stores no dXb / dXz / dXo,
+ *     and dGl only for an image gradient; its first layers read Xb's [features | context] columns in place of Xz's / Xo's);
+ *     Za, Za16: the decoder's input (z_attr; fp32 from the per-wavefront launches, its bf16 copy in the bf16 step)
+ *   decoder: Hd1, Hd2, dHd1, dHd2 (hidden layers and their gradients, the step's dtype), S (sprite logits / sprites: fp16 or fp32 as
+ *     spair_step_plan's s16), dLog (d logits: bf16 or fp32 as its g16), dLog16 (bf16 copy of fp32 d logits, bf16 step)
+ *   backbone (NHWC, one row per pixel): xpad (padded input, fp32), act<i> / dact<i> (output of layer i = 0 .. n_conv - 1 and its gradient, the
+ *     step's dtype; dact0 is not written where conv_1's data gradient takes the stem's weight gradient), feat / dfeat (conv_out's output
+ *     and its gradient, fp32, N rows; dfeat is not written by the fused chain), dfeat16 (bf16 copy of dfeat, bf16 step)
+ *   prepared weights (the step's dtype, zero padded to the leading dimension): conv_wf<i> (layer i = 1 .. n_conv: [cout][k k cin], taps
+ *     (ky, kx) outer, or the tap-parity K order of the bf16 strided convs with cin % 64 == 0), conv_wd<i>_<q> (its data-gradient matrix of
+ *     output-parity class q = py s + px: [cin][(ty T + tx) cout + co] of W[co][ci][py + s ty][px + s tx], T = k / s; 1x1: [cin][cout]),
+ *     lin_wf.<layer> ([out][in]) and lin_wt.<layer> ([in][out]) per dense layer, named as its parameters without ".weight" (the two
+ *     output layers of a head share one matrix: output_layers.0 sits behind output_layers.1's rows / columns). */
+int spair_workspace_view(const SpairDims* d, const void* workspace, int flags, int input_grad, const char* name, long long* out);
+/* the idx-th name spair_workspace_view resolves on these dims (the buffers they allocate), or SPAIR_ERR_SHAPE past the last one */
+int spair_workspace_view_name(const SpairDims* d, int idx, char* name, int name_cap);
 /* wavefronts walked by the workgroup that stamps (sample 0; with the band split of grids wider than 16 cells, its top band) */
 int spair_chain_stamp_wavefronts(const SpairDims* d);
 /* band split of the fused per-cell kernels (grids wider than 16 cells: ceil(G / 8) workgroups per sample hand the boundary rows' records /

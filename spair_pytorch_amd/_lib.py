@@ -87,3 +87,24 @@ def step_plan_n(dims, workspace, flags=0, input_grad=False):
     return dict(side=bool(out[8]), dec_dgrad_fused=bool(out[9]), dec_wgrad_grouped=bool(out[10]), dec_wgrad_late=bool(out[11]), pw0=out[12],
                 stem=STEM_WGRADS[out[13]], fwd=tuple(CONV_KERNELS[out[14 + i]] for i in layers),
                 dgrad=tuple(CONV_KERNELS[out[22 + i]] for i in layers), gate_bits=tuple(bool(out[30 + i]) for i in layers))
+
+
+VIEW_DTYPES = (torch.float32, torch.bfloat16, torch.float16)     # spair_workspace_view's element types 0, 1, 2
+
+
+def workspace_view_names(dims):
+    """Every buffer name spair_workspace_view resolves on these SpairDims (the buffers their workspace allocates).  Host only."""
+    f, buf, names = lib().spair_workspace_view_name, ctypes.create_string_buffer(128), []
+    while f(ctypes.byref(dims), len(names), buf, 128) == 0:
+        names.append(buf.value.decode())
+    return names
+
+
+def workspace_view(dims, workspace, name, flags=0, input_grad=False):
+    """spair_workspace_view: where buffer ``name`` lies in a workspace at address ``workspace`` (an int; never read) for the step plan of
+    SpairStep.flags ``flags`` and an image gradient or not, as {offset (bytes), rows, cols, ld (elements), dtype (a torch dtype), written}.
+    Host only: no GPU is needed."""
+    out = (ctypes.c_longlong * 6)()
+    check(lib().spair_workspace_view(ctypes.byref(dims), ctypes.c_void_p(int(workspace)), int(flags), int(bool(input_grad)),
+                                     name.encode(), out), "spair_workspace_view(%s)" % name)
+    return dict(offset=out[0], rows=out[1], cols=out[2], ld=out[3], dtype=VIEW_DTYPES[out[4]], written=bool(out[5]))

@@ -1654,6 +1654,145 @@ extern "C" int spair_step_plan(const SpairDims* d, const void* workspace, int fl
     return spair_step_plan_n(d, workspace, flags, 0, out, 8);
 }
 
+// ---- workspace view (diagnostic) -----------------------------------------------------------------------------
+// Every named buffer of the step's workspace (include/spair_hip.h lists the names): where carve() put it, its rows, meaningful columns, leading
+// dimension in elements, element type (0 fp32, 1 bf16, 2 fp16) as the step plan of (flags, input_grad) writes it, and whether that plan writes
+// it.  p == nullptr: not allocated on this workspace.  Host arithmetic only.
+struct WsItem { char name[96]; const void* p; long long rows, cols, ld; int type, written; };
+
+static const char* lin_param_name(const ParamLayout& PL, int id) {
+    static const char* mlp[LIN_COUNT] = {"box_network.body.dense0", "box_network.body.dense1", "box_network.output_layers.0",
+                                         "box_network.output_layers.1", "object_encoder.dense0", "object_encoder.dense1", "object_encoder.out",
+                                         "z_network.body.dense0", "z_network.body.dense1", "z_network.output_layers.0", "z_network.output_layers.1",
+                                         "obj_network.dense0", "obj_network.dense1", "obj_network.out", "object_decoder.dense0",
+                                         "object_decoder.dense1", "object_decoder.out"};
+    if (PL.oc_n && id == LIN_DEC0) return "object_decoder.inp";
+    return mlp[id];
+}
+
+static std::vector<WsItem> ws_items(const SpairDims& d, const void* base, int flags, bool input_grad) {
+    const Ws w = carve(d, const_cast<void*>(base));
+    const StepPlan p = plan_step(d, flags, input_grad, base);
+    const CellLayout L = make_cell_layout(d);
+    const ParamLayout PL = make_param_layout(d);
+    const CellBufs& b = w.cb;
+    const bool b16 = d.dtype == SPAIR_BF16, oc = PL.oc_n > 0, chain = p.use_chain;
+    const int et = b16 ? 1 : 0;
+    const long long N = L.N;
+    std::vector<WsItem> v;
+    auto add = [&](const char* name, const void* ptr, long long rows, long long cols, long long ld, int type, bool written) {
+        WsItem it;
+        snprintf(it.name, sizeof(it.name), "%s", name);
+        it.p = ptr; it.rows = rows; it.cols = cols; it.ld = ld; it.type = type; it.written = written ? 1 : 0;
+        v.push_back(it);
+    };
+    // per-cell rows: bf16 from the fused chain (except its fp32 head outputs O*), fp32 from the per-wavefront launches.  The fused chain keeps
+    // no input-row gradients (d Xb, d Xz, d Xo; d glimpse only for an image gradient, as an fp32 GEMM output)
+    const int rt = chain ? 1 : 0;
+    auto row = [&](const char* name, const void* ptr, int cols, int ld, bool o, bool written) { add(name, ptr, N, cols, ld, o ? 0 : rt, written); };
+    const bool enc = !oc;      // the MLP encoder's hidden layers
+    row("Xb", b.Xb, L.F + L.CTX, L.ld_xb, false, true);
+    row("Hb1", b.Hb1, SP_H, SP_LDH, false, true); row("Hb2", b.Hb2, SP_H, SP_LDH, false, true);
+    row("Ob", b.Ob, L.NP + 8, L.ld_ob, true, true);
+    row("glimpse", b.glimpse, L.glimpse, L.ld_gl, false, true);
+    row("He1", b.He1, SP_ENC_H1, SP_ENC_H1, false, enc); row("He2", b.He2, SP_ENC_H2, SP_ENC_H2, false, enc);
+    row("Oe", b.Oe, 2 * L.A, L.ld_oe, true, true);
+    row("Xz", b.Xz, L.x_depth, L.ld_x, false, true);
+    row("Hz1", b.Hz1, SP_H, SP_LDH, false, true); row("Hz2", b.Hz2, SP_H, SP_LDH, false, true);
+    row("Oz", b.Oz, L.NP + 2, L.ld_oz, true, true);
+    row("Xo", b.Xo, L.x_depth + 1, L.ld_x, false, true);
+    row("Ho1", b.Ho1, SP_H, SP_LDH, false, true); row("Ho2", b.Ho2, SP_H, SP_LDH, false, true);
+    row("Oo", b.Oo, 1, L.ld_oo, true, true);
+    row("dXb", b.dXb, L.F + L.CTX, L.ld_xb, false, !chain);
+    row("dHb1", b.dHb1, SP_H, SP_LDH, false, true); row("dHb2", b.dHb2, SP_H, SP_LDH, false, true);
+    row("dOb", b.dOb, L.NP + 8, L.ld_ob, false, true);
+    add("dGl", b.dGl, N, L.glimpse, L.ld_gl, 0, !chain || input_grad);
+    row("dHe1", b.dHe1, SP_ENC_H1, SP_ENC_H1, false, enc); row("dHe2", b.dHe2, SP_ENC_H2, SP_ENC_H2, false, enc);
+    row("dOe", b.dOe, 2 * L.A, L.ld_oe, false, true);
+    row("dXz", b.dXz, L.x_depth, L.ld_x, false, !chain);
+    row("dHz1", b.dHz1, SP_H, SP_LDH, false, true); row("dHz2", b.dHz2, SP_H, SP_LDH, false, true);
+    row("dOz", b.dOz, L.NP + 2, L.ld_oz, false, true);
+    row("dXo", b.dXo, L.x_depth + 1, L.ld_x, false, !chain);
+    row("dHo1", b.dHo1, SP_H, SP_LDH, false, true); row("dHo2", b.dHo2, SP_H, SP_LDH, false, true);
+    row("dOo", b.dOo, 1, L.ld_oo, false, true);
+    add("Za", w.Za, N, L.A, L.ld_rec, 0, !chain);
+    add("Za16", w.Za16, N, L.A, L.ld_rec, 1, b16);
+    // decoder
+    const int per = d.P * d.P * (d.C + 1);
+    add("Hd1", w.Hd1, N, SP_DEC_H1, SP_DEC_H1, et, !oc); add("Hd2", w.Hd2, N, SP_DEC_H2, SP_DEC_H2, et, !oc);
+    add("dHd1", w.dHd1, N, SP_DEC_H1, SP_DEC_H1, et, !oc); add("dHd2", w.dHd2, N, SP_DEC_H2, SP_DEC_H2, et, !oc);
+    add("S", w.S, N, per, w.ld_s, p.rp.s16 ? 2 : 0, true);
+    add("dLog", w.dLog, N, per, w.ld_s, p.rp.g16 ? 1 : 0, true);
+    add("dLog16", w.dLog16, N, per, w.ld_s, 1, true);
+    // backbone (NHWC rows: one per pixel)
+    const int Ip = d.I + d.pad_pre + d.pad_post, Ipw = d.Iw + d.pad_pre + d.pad_post_w;
+    add("xpad", w.xpad, (long long)d.B * Ip * Ipw, d.C, d.C, 0, true);
+    char nm[96];
+    for (int i = 0; i < d.n_conv; ++i) {
+        const ConvSpec& cs = PL.conv[i];
+        const long long px = (long long)d.B * cs.hout * cs.wout;
+        snprintf(nm, sizeof(nm), "act%d", i); add(nm, w.act[i], px, cs.cout, cs.cout, et, true);
+        // conv_1's data gradient that takes the stem's weight gradient from its tile never stores d act0
+        snprintf(nm, sizeof(nm), "dact%d", i); add(nm, w.dact[i], px, cs.cout, cs.cout, et, i > 0 || (p.stem_wgrad != STEM_PATCH && p.stem_wgrad != STEM_GEMM));
+    }
+    add("feat", w.feat, N, d.F, w.ld_feat, 0, true);
+    add("dfeat", w.dfeat, N, d.F, w.ld_feat, 0, !chain);
+    add("dfeat16", w.dfeat16, N, d.F, w.ld_feat, 1, true);
+    // prepared weights
+    for (int i = 1; i < PL.n_conv; ++i) {
+        const ConvSpec& cs = PL.conv[i];
+        const int K = cs.k * cs.k * cs.cin;
+        snprintf(nm, sizeof(nm), "conv_wf%d", i); add(nm, w.conv_wf[i], cs.cout, K, round_up(K, 8), et, true);
+        if (cs.k == 1) { snprintf(nm, sizeof(nm), "conv_wd%d_0", i); add(nm, w.conv_wd[i][0], cs.cin, cs.cout, round_up(cs.cout, 8), et, true); }
+        else for (int q = 0; q < cs.s * cs.s; ++q) {
+            const int T = cs.k / cs.s;
+            snprintf(nm, sizeof(nm), "conv_wd%d_%d", i, q); add(nm, w.conv_wd[i][q], cs.cin, T * T * cs.cout, T * T * cs.cout, et, true);
+        }
+    }
+    for (int id = 0; id < LIN_COUNT; ++id) {
+        const LinSpec& l = PL.lin[id];
+        if (!l.in || !l.out) continue;
+        const int slot = id == LIN_BOXH0 ? LIN_BOXH1 : id == LIN_ZH0 ? LIN_ZH1 : id;       // a head's two layers share one matrix: [pass | lat]
+        const int head0 = slot == LIN_BOXH1 ? LIN_BOXH0 : slot == LIN_ZH1 ? LIN_ZH0 : -1;
+        const int rows_total = PL.lin[slot].out + (head0 >= 0 ? PL.lin[head0].out : 0);
+        const int ldf = round_up(l.in, 8), ldt = round_up(rows_total, 8);
+        const size_t r0 = id == head0 ? (size_t)PL.lin[slot].out : 0;
+        const char* pn = lin_param_name(PL, id);
+        snprintf(nm, sizeof(nm), "lin_wf.%s", pn);
+        add(nm, w.lin_wf[slot] ? bptr(w.lin_wf[slot], r0 * ldf, d.dtype) : nullptr, l.out, l.in, ldf, et, true);
+        snprintf(nm, sizeof(nm), "lin_wt.%s", pn);
+        add(nm, w.lin_wt[slot] ? bptr(w.lin_wt[slot], r0, d.dtype) : nullptr, l.in, l.out, ldt, et, true);
+    }
+    return v;
+}
+
+extern "C" int spair_workspace_view(const SpairDims* d0, const void* workspace, int flags, int input_grad, const char* name, long long* out) {
+    if (!d0 || !workspace || !name || !out) return SPAIR_ERR_SHAPE;
+    const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
+    TRY(validate(*d));
+    for (const WsItem& it : ws_items(*d, workspace, flags, input_grad != 0)) {
+        if (strcmp(it.name, name) != 0) continue;
+        if (!it.p) return SPAIR_ERR_UNSUPPORTED;
+        const long long v[6] = {(long long)(reinterpret_cast<const char*>(it.p) - reinterpret_cast<const char*>(workspace)), it.rows, it.cols, it.ld,
+                                it.type, it.written};
+        for (int i = 0; i < 6; ++i) out[i] = v[i];
+        return SPAIR_OK;
+    }
+    return SPAIR_ERR_SHAPE;
+}
+
+extern "C" int spair_workspace_view_name(const SpairDims* d0, int idx, char* name, int name_cap) {
+    if (!d0 || !name || name_cap < 1) return SPAIR_ERR_SHAPE;
+    const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
+    TRY(validate(*d));
+    int k = 0;
+    for (const WsItem& it : ws_items(*d, reinterpret_cast<const void*>((uintptr_t)1 << 30), 0, false)) {
+        if (!it.p) continue;
+        if (k++ == idx) { snprintf(name, name_cap, "%s", it.name); return SPAIR_OK; }
+    }
+    return SPAIR_ERR_SHAPE;
+}
+
 // band split of the fused chain kernels: 1 if a wait for the neighbouring band ever timed out in a launch on this workspace (STICKY: no
 // launch clears it; the step's loss and edge-element gradient are NaN from then on -- never seen, the test suite asserts 0), else 0; -1 where
 // the chain runs unsplit.  Copies one int to `out` (device).

@@ -572,6 +572,22 @@ class SPAIR(nn.Module):
         e = self._engine(batch)
         return L.step_plan(e["dims"], e["workspace"].data_ptr(), STEP_FLAGS)
 
+    def workspace_view(self, name, batch=None, padded=False):
+        """A torch view (no copy) of buffer ``name`` of the workspace of batch size ``batch`` (default: the latest forward's) as the
+        current ``STEP_FLAGS`` lay it out: [rows, cols] of its element type (``padded``: [rows, ld], the padding included).  Names and
+        meaning: include/spair_hip.h, spair_workspace_view.  Nothing is aliased in the workspace, so after a step the view holds what that
+        step's kernels read and wrote; it is valid until the next forward on that workspace (which overwrites it) or until the engine cache
+        drops the workspace.  A diagnostic for tests: it does not synchronise."""
+        if padded and name.startswith("lin_wt.") and name.endswith("output_layers.0"):
+            raise ValueError("%s starts inside the rows it shares with its head's first layer: it has no padded view of its own" % name)
+        e = self._last_engine() if batch is None else self._engine(batch)
+        ws = e["workspace"]
+        v = L.workspace_view(e["dims"], ws.data_ptr(), name, STEP_FLAGS)
+        es = torch.empty((), dtype=v["dtype"]).element_size()
+        width = v["ld"] if padded else v["cols"]
+        t = ws[v["offset"]:v["offset"] + ((v["rows"] - 1) * v["ld"] + width) * es].view(v["dtype"])     # (no element past the last row)
+        return t.as_strided((v["rows"], width), (v["ld"], 1))
+
     def chain_status(self):
         """Band-split hand-off status of the latest forward's workspace (grids wider than 16 cells): -1 where the chain runs unsplit, 0 = every
         hand-off arrived, 1 = a wait timed out (sticky; that step's loss and every later one is NaN).  SYNCHRONISES -- call it where the
