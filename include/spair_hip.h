@@ -66,8 +66,9 @@ typedef struct SpairDims {
     int Iw, Gw, pad_post_w;
 } SpairDims;
 
-/* Version of the layouts of SpairDims and SpairStep (and of the entry points' argument lists): a binding checks it before it passes a struct. */
-#define SPAIR_ABI_VERSION 2
+/* Version of the layouts of SpairDims, SpairStep and SpairStepIO (and of the entry points' argument lists): a binding checks it before it
+ * passes a struct. */
+#define SPAIR_ABI_VERSION 3
 int spair_abi_version(void);
 
 /* Per-step scalars (host side evaluates the two schedules, modules.py:191-213). */
@@ -76,15 +77,15 @@ typedef struct SpairStep {
     float count_prior_prob;    /* 1/(1+exp(-log(v+1e-6))), models.py:186-188 */
     float kl_scale;            /* 1/(B*world_size): batch-mean of the KL terms (models.py:553) */
     int train;                 /* 1: keep what backward needs */
-    int flags;                 /* bits 0 and 2-6 are inputs of the step's kernel plan (spair_step_plan_n); bit 1 is not.
+    int flags;                 /* bits 0 and 2-6 are inputs of the step's kernel plan (spair_step_plan); bit 1 is not.
                                 * bit 0: disable the fused persistent per-cell kernels (A/B testing); bit 1: record stage stamps;
                                 * bit 2: no helper stream (every kernel on the caller's stream);
                                 * bit 3: stem weight gradient as its own kernel (not fused into conv_1's data gradient);
                                 * bit 4: decoder forward as three GEMM launches instead of the fused activation-stationary kernel;
                                 * bit 5: strided backbone convs through the implicit-GEMM kernel instead of the patch-resident one;
                                 * bit 6: decoder data gradients as three GEMM launches instead of the fused kernel */
-    int draw_noise;            /* spair_forward only: 1 = fill eps_box/eps_attr/eps_depth/u_pres from noise_seed first (what spair_noise_fill
-                                * does, but on the helper stream beside the backbone); the buffers must be writable */
+    int draw_noise;            /* spair_forward only: 1 = fill SpairStepIO's four noise maps from noise_seed first (what spair_noise_fill
+                                * does, but on the helper stream beside the backbone) */
     unsigned long long noise_seed;
     /* Non-finite / failed steps made loud without a host synchronisation (the reference RAISES on any NaN in its forward:
      * spair/debug_tools.py:245-271, called at models.py:65,108,245).  spair_forward's loss kernel evaluates
@@ -109,56 +110,57 @@ int64_t spair_workspace_bytes(const SpairDims* d);
 
 /* ---- the training step ---------------------------------------------------------------------
  * forward  == SPAIR.forward (models.py:35-131): backbone -> per-cell loop -> KL -> render -> loss.
- *   loss_out (>= 10 floats): [0]=total, [1]=BCE sum, [2..8]=KL cy,cx,height,width,attr,depth,pres (batch means), [9]=total again (a
- *   second copy for a host layer that hands the loss out as a view: an in-place op on it then leaves the logged terms [0..8] alone).
  * backward == loss.backward() (train.py:66): accumulates into `grads` (same layout as params).
- * Noise maps are NCHW: eps_box[B,4,G,Gw] (cy,cx,height,width), eps_attr[B,A,G,Gw],
- * eps_depth[B,1,G,Gw], u_pres[B,1,G,Gw]; x and recon [B,C,I,Iw]; z_where [B,4,G,Gw], z_pres [B,1,G,Gw]. */
-int spair_forward(const SpairDims* d, const SpairStep* st, const float* params, const float* x,
-                  const float* eps_box, const float* eps_attr, const float* eps_depth, const float* u_pres,
-                  void* workspace, float* loss_out, float* recon, float* z_where, float* z_pres, void* stream);
-int spair_backward(const SpairDims* d, const SpairStep* st, const float* params, const float* x,
-                   const float* eps_box, const float* eps_attr, const float* eps_depth, const float* u_pres,
-                   void* workspace, const float* grad_loss, float* grads, void* stream);
-/* Data-parallel hook (the reference is single-device, train.py:27-30): the backward completes the gradients in three
- * contiguous ranges of `grads` -- [0] decoder, [1] box/encoder/z/obj nets, [2] edge element + backbone, in that order.
- * spair_grad_buckets returns the ranges (element offsets); spair_backward_ev is spair_backward that additionally records the
- * caller-created hipEvent_t ev_* (null = skip) when the corresponding range is final, so its all-reduce can overlap the rest. */
+ * Both take the step's device memory in one SpairStepIO.  An optional field may be NULL: that part of the step is left out and launches
+ * nothing, so a backward with every optional field NULL is the plain backward, kernel for kernel.  Maps are NCHW. */
+typedef struct SpairStepIO {
+    /* read by both directions: the backward takes the buffers of the forward (SpairStep.train = 1) it follows.  None may be NULL. */
+    const float* params;       /* flat fp32 parameters (spair_param_info) */
+    const float* x;            /* input image [B,C,I,Iw] */
+    float* eps_box;            /* noise maps: [B,4,G,Gw] (cy,cx,height,width), */
+    float* eps_attr;           /*   [B,A,G,Gw], */
+    float* eps_depth;          /*   [B,1,G,Gw], */
+    float* u_pres;             /*   [B,1,G,Gw]; spair_forward writes all four first when SpairStep.draw_noise is set */
+    void* workspace;           /* spair_workspace_bytes(d) bytes, zeroed once by the caller */
+    /* spair_forward */
+    float* loss_out;           /* >= 10 floats: [0]=total, [1]=BCE sum, [2..8]=KL cy,cx,height,width,attr,depth,pres (batch means), [9]=total
+                                * again (a second copy for a host layer that hands the loss out as a view: an in-place op on it then leaves
+                                * the logged terms [0..8] alone) */
+    float* recon;              /* [B,C,I,Iw] */
+    float* z_where;            /* [B,4,G,Gw] */
+    float* z_pres;             /* [B,1,G,Gw] */
+    float* inv_den;            /* optional: [B][I][Iw], 1/D of the renderer's composite per pixel, kept for a backward with grad_recon */
+    /* spair_backward */
+    const float* grad_loss;    /* one float; may point at a zero for a backward through the outputs alone */
+    float* grads;              /* accumulated into */
+    /* Data-parallel hook (the reference is single-device, train.py:27-30): the backward completes the gradients in three
+     * contiguous ranges of `grads` (spair_grad_buckets) in this order.  Optional caller-created hipEvent_t, recorded when its range is
+     * final, so that its all-reduce can overlap the rest. */
+    void* ev_decoder;          /* decoder */
+    void* ev_cells;            /* box / encoder / z / obj nets */
+    void* ev_backbone;         /* edge element + backbone */
+    /* Differentiable outputs (the reference returns recon, z_where and z_pres as autograd tensors, models.py:35-131, so a user term on any
+     * of them trains through the model).  Optional adjoints of the three outputs, folded into the reverse pass element for element, no
+     * atomics: deterministic. */
+    const float* grad_recon;   /* [B,C,I,Iw]: needs the inv_den of the same forward and aux_scratch, else SPAIR_ERR_SHAPE */
+    const float* grad_z_where; /* [B,4,G,Gw] */
+    const float* grad_z_pres;  /* [B,1,G,Gw] */
+    float* aux_scratch;        /* 2*B*C*I*Iw + 1 floats, only touched with grad_recon (the workspace keeps what the forward saved, so a
+                                * second backward through the same forward is unaffected) */
+    /* Optional: the gradient of the step with respect to its input image, OVERWRITTEN, fp32 [B,C,I,Iw]: the backbone term (the stem's data
+     * gradient from d act0), the glimpse term (the adjoint of the border-padded STN glimpse) and, with bce_target != 0, the BCE-target term
+     * *grad_loss * (log1p(-recon) - log(recon)) -- torch's gradient of binary_cross_entropy with respect to its target, not clamped: +inf
+     * where recon == 0, -inf where recon == 1 (the status word is not affected).  Its kernels run after ev_backbone is recorded; no atomics
+     * on grad_x: deterministic.  SPAIR_ERR_UNSUPPORTED for fewer than 2 backbone layers or a stem of more than 64 KiB of weights. */
+    float* grad_x;
+    void* x_scratch;           /* spair_input_grad_scratch_bytes(d) bytes: needed with grad_x, else SPAIR_ERR_SHAPE */
+    int bce_target;            /* with grad_x; 0 is for a backward through the outputs alone, where the loss is not part of the graph */
+} SpairStepIO;
+int spair_forward(const SpairDims* d, const SpairStep* st, const SpairStepIO* io, void* stream);
+int spair_backward(const SpairDims* d, const SpairStep* st, const SpairStepIO* io, void* stream);
+/* the three ranges of SpairStepIO.ev_*, as element offsets [lo, hi) into `grads` */
 int spair_grad_buckets(const SpairDims* d, int64_t* lo3, int64_t* hi3);
-int spair_backward_ev(const SpairDims* d, const SpairStep* st, const float* params, const float* x,
-                      const float* eps_box, const float* eps_attr, const float* eps_depth, const float* u_pres,
-                      void* workspace, const float* grad_loss, float* grads, void* stream,
-                      void* ev_decoder, void* ev_cells, void* ev_backbone);
-/* Differentiable outputs (the reference returns recon, z_where and z_pres as autograd tensors, models.py:35-131, so a user term on any of
- * them trains through the model).  spair_forward_out is spair_forward that also keeps inv_den [B][I][Iw] (1/D of the renderer's composite per
- * pixel; NULL = not kept).  spair_backward_out is spair_backward_ev that also folds the adjoints of the three outputs into the reverse pass:
- * grad_recon [B,C,I,Iw] (needs the inv_den of the same forward, else SPAIR_ERR_SHAPE), grad_z_where [B,4,G,Gw], grad_z_pres [B,1,G,Gw]; any of
- * them may be NULL, and one that is NULL launches nothing (all three NULL = spair_backward_ev, kernel for kernel).  grad_loss may point at a
- * zero for a backward through the outputs alone.  aux_scratch: 2*B*C*I*Iw + 1 floats, only touched with grad_recon (the workspace keeps
- * what the forward saved, so a second backward through the same forward is unaffected).  Element for element, no atomics: deterministic. */
-int spair_forward_out(const SpairDims* d, const SpairStep* st, const float* params, const float* x,
-                      const float* eps_box, const float* eps_attr, const float* eps_depth, const float* u_pres,
-                      void* workspace, float* loss_out, float* recon, float* z_where, float* z_pres, void* stream, float* inv_den);
-int spair_backward_out(const SpairDims* d, const SpairStep* st, const float* params, const float* x,
-                       const float* eps_box, const float* eps_attr, const float* eps_depth, const float* u_pres,
-                       void* workspace, const float* grad_loss, float* grads, void* stream,
-                       void* ev_decoder, void* ev_cells, void* ev_backbone,
-                       const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
-                       float* aux_scratch);
-/* spair_backward_x: spair_backward_out that also writes the gradient of the step with respect to its input image into grad_x [B,C,I,Iw]
- * (OVERWRITTEN, fp32): the backbone term (the stem's data gradient from d act0), the glimpse term (the adjoint of the border-padded STN
- * glimpse) and, with bce_target != 0, the BCE-target term *grad_loss * (log1p(-recon) - log(recon)) -- torch's gradient of
- * binary_cross_entropy with respect to its target, not clamped: +inf where recon == 0, -inf where recon == 1 (the status word is not
- * affected).  bce_target = 0 is for a backward through the outputs alone, where the loss is not part of the graph.  These kernels run
- * after ev_backbone is recorded.  x_scratch: spair_input_grad_scratch_bytes(d) bytes.  grad_x == NULL is spair_backward_out, kernel for
- * kernel.  No atomics on grad_x: deterministic. */
-int spair_backward_x(const SpairDims* d, const SpairStep* st, const float* params, const float* x,
-                     const float* eps_box, const float* eps_attr, const float* eps_depth, const float* u_pres,
-                     void* workspace, const float* grad_loss, float* grads, void* stream,
-                     void* ev_decoder, void* ev_cells, void* ev_backbone,
-                     const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
-                     float* aux_scratch, float* grad_x, int bce_target, void* x_scratch);
-/* host arithmetic only: bytes of spair_backward_x's x_scratch (-1 for invalid dims); never part of spair_workspace_bytes */
+/* host arithmetic only: bytes of SpairStepIO.x_scratch (-1 for invalid dims); never part of spair_workspace_bytes */
 int64_t spair_input_grad_scratch_bytes(const SpairDims* d);
 /* torch.optim.Adam(lr) defaults (train.py:44) on flat buffers, one launch. */
 int spair_adam(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
@@ -185,7 +187,7 @@ int spair_chain_stamps(const SpairDims* d, const void* workspace, unsigned long 
  * sampling interval (K4: modules.py:216-273 via models.py:387) among them, stamps per wavefront of the backward kernel (from offset 2048) */
 int spair_chain_stamp_layout(int* fwd_per_wavefront, int* fwd_glimpse_interval, int* bwd_per_wavefront);
 /* diagnostic: the kernels spair_forward / spair_backward choose for these dims, this workspace, SpairStep.flags `flags` and, for the
- * backward, whether an image gradient is requested (input_grad: spair_backward_x with grad_x).  Host arithmetic only: of workspace only
+ * backward, whether an image gradient is requested (input_grad: SpairStepIO.grad_x non-NULL).  Host arithmetic only: of workspace only
  * the address's 16-byte alignment is read (it must not be NULL; nothing is dereferenced, nothing is launched).  Writes the first min(n, SPAIR_STEP_PLAN_INTS) of these ints to host `out`:
  *   [0..7]   the renderer family of the forward and of the backward (SPAIR_RENDER_*), then 0/1 for: per-object records (render_prep), fp16
  *            sprites, bf16 d-logits, the fused per-cell chain kernels, the fused decoder forward; out[7] = 0;
@@ -210,11 +212,9 @@ int spair_chain_stamp_layout(int* fwd_per_wavefront, int* fwd_glimpse_interval, 
 #define SPAIR_STEM_GEMM 1       /* fused into the epilogue of conv_1's implicit-GEMM data gradient */
 #define SPAIR_STEM_WGRAD16 2    /* its own kernel (grey-scale 4x4 stem, bf16 step) */
 #define SPAIR_STEM_GENERIC 3    /* the TN GEMM (fp32 step, other stems) */
-int spair_step_plan_n(const SpairDims* d, const void* workspace, int flags, int input_grad, int* out, int n);
-/* the first 8 ints of spair_step_plan_n without an image gradient */
-int spair_step_plan(const SpairDims* d, const void* workspace, int flags, int* out);
-/* diagnostic: where the buffer `name` of a step's workspace lies, for the step plan of (flags, input_grad) as spair_step_plan_n takes them.
- * Host arithmetic only, as spair_step_plan_n (workspace is an address, never dereferenced).  Writes to host `out`: [0] byte offset from
+int spair_step_plan(const SpairDims* d, const void* workspace, int flags, int input_grad, int* out, int n);
+/* diagnostic: where the buffer `name` of a step's workspace lies, for the step plan of (flags, input_grad) as spair_step_plan takes them.
+ * Host arithmetic only, as spair_step_plan (workspace is an address, never dereferenced).  Writes to host `out`: [0] byte offset from
  * workspace, [1] rows, [2] meaningful columns, [3] leading dimension in elements, [4] element type (0 fp32, 1 bf16, 2 fp16) as that plan
  * writes the buffer, [5] 1 if that plan's training step (forward + backward) writes it, else 0.  No buffer is aliased: the regions never
  * overlap, and every one keeps what the last step left until the next step on the workspace.  Returns SPAIR_ERR_SHAPE for an unknown name,
@@ -331,7 +331,7 @@ int spair_stn_glimpse_fwd(const float* x, const float* nbox, int B, float* glimp
                           int I, int P, int align_corners, void* stream);
 int spair_stn_glimpse_bwd(const float* x, const float* nbox, int B, const float* dglimpse, int ld_gl,
                           float* dnbox, int R, int C, int I, int P, int align_corners, void* stream);
-/* The two kernels of spair_backward_x's image gradient on their own (csrc/input_grad.hip).
+/* The two kernels of the step's image gradient (SpairStepIO.grad_x) on their own (csrc/input_grad.hip).
  * spair_input_grad_glimpse: adjoint of spair_stn_glimpse_fwd with respect to the IMAGE.  Rows r = k*B + b (k < ncell) of dglimpse
  * [rows][ld_gl] ((c, i, j) order) and nbox [rows][4]; out [B,C,I,I] = sum over k of sample b's rows, overwritten, deterministic.
  * spair_input_grad_stem: data gradient of the stem conv (weights w [Cout,C,k,k], stride s) from dact0 [B,Hout,Hout,Cout] (fp32, or bf16 with

@@ -17,11 +17,47 @@ _ERR = {-1: "bad shape", -2: "unsupported dtype", -3: "kernel launch failed", -4
         -5: "misaligned leading dimension / size"}
 
 _lib = None
-ABI_VERSION = 2          # SPAIR_ABI_VERSION (include/spair_hip.h)
+ABI_VERSION = 3          # SPAIR_ABI_VERSION (include/spair_hip.h)
 
 
 class SpairHipError(RuntimeError):
     pass
+
+
+# mirrors of the structs of include/spair_hip.h (tests/test_abi_layout_cpu.py holds them to the header's sizes and offsets)
+class SpairDims(ctypes.Structure):
+    """include/spair_hip.h :: SpairDims"""
+    _fields_ = [("B", ctypes.c_int), ("C", ctypes.c_int), ("I", ctypes.c_int), ("G", ctypes.c_int),
+                ("P", ctypes.c_int), ("A", ctypes.c_int), ("F", ctypes.c_int), ("NP", ctypes.c_int),
+                ("n_conv", ctypes.c_int), ("conv_k", ctypes.c_int * 8), ("conv_s", ctypes.c_int * 8),
+                ("conv_c", ctypes.c_int * 8), ("pad_pre", ctypes.c_int), ("pad_post", ctypes.c_int),
+                ("cell_px", ctypes.c_int), ("dtype", ctypes.c_int), ("align_corners", ctypes.c_int),
+                ("anchor", ctypes.c_float), ("max_yx", ctypes.c_float), ("min_yx", ctypes.c_float),
+                ("max_hw", ctypes.c_float), ("min_hw", ctypes.c_float), ("obj_logit_scale", ctypes.c_float),
+                ("alpha_logit_scale", ctypes.c_float), ("alpha_logit_bias", ctypes.c_float),
+                ("vae_beta", ctypes.c_float), ("prior_mean", ctypes.c_float * 6), ("prior_std", ctypes.c_float * 6),
+                ("obj_conv", ctypes.c_int), ("oc_n", ctypes.c_int), ("oc_k", ctypes.c_int * 4), ("oc_s", ctypes.c_int * 4),
+                ("oc_c", ctypes.c_int * 4), ("lookback", ctypes.c_int),
+                ("Iw", ctypes.c_int), ("Gw", ctypes.c_int), ("pad_post_w", ctypes.c_int)]
+
+
+class SpairStep(ctypes.Structure):
+    """include/spair_hip.h :: SpairStep"""
+    _fields_ = [("wheel", ctypes.c_float), ("count_prior_prob", ctypes.c_float), ("kl_scale", ctypes.c_float),
+                ("train", ctypes.c_int), ("flags", ctypes.c_int), ("draw_noise", ctypes.c_int), ("noise_seed", ctypes.c_uint64),
+                ("status", ctypes.c_void_p), ("status_host", ctypes.c_void_p)]
+
+
+class SpairStepIO(ctypes.Structure):
+    """include/spair_hip.h :: SpairStepIO (an unset field is NULL)"""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        "params", "x", "eps_box", "eps_attr", "eps_depth", "u_pres", "workspace",
+        "loss_out", "recon", "z_where", "z_pres", "inv_den",
+        "grad_loss", "grads", "ev_decoder", "ev_cells", "ev_backbone",
+        "grad_recon", "grad_z_where", "grad_z_pres", "aux_scratch", "grad_x", "x_scratch")] + [("bce_target", ctypes.c_int)]
+
+
+_STEP_ARGS = [ctypes.POINTER(SpairDims), ctypes.POINTER(SpairStep), ctypes.POINTER(SpairStepIO), ctypes.c_void_p]
 
 
 def lib():
@@ -32,12 +68,16 @@ def lib():
                 "libspair_hip.so is not built (%s). Run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `python -m spair_pytorch_amd._build`. There is no CPU/PyTorch fallback." % LIB_PATH)
         h = ctypes.CDLL(LIB_PATH)
-        # the structs this package passes (models.SpairDims / SpairStep) must be the ones the library reads: a stale build with a shorter
-        # SpairDims would read past the end of the caller's struct
+        # the structs this package passes must be the ones the library reads: a stale build with a shorter SpairDims would read past
+        # the end of the caller's struct
         got = h.spair_abi_version() if hasattr(h, "spair_abi_version") else None
         if got != ABI_VERSION:
             raise SpairHipError("%s has ABI version %s, this package needs %d: rebuild it (python -m spair_pytorch_amd._build)"
                                 % (LIB_PATH, got, ABI_VERSION))
+        for f, args in ((h.spair_forward, _STEP_ARGS), (h.spair_backward, _STEP_ARGS),
+                        (h.spair_step_plan, [ctypes.POINTER(SpairDims), ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_int), ctypes.c_int])):
+            f.argtypes, f.restype = args, ctypes.c_int
         _lib = h
     return _lib
 
@@ -65,7 +105,7 @@ def step_plan(dims, workspace, flags=0):
     """spair_step_plan: the kernels a step with these SpairDims, workspace address (an int; never read) and SpairStep.flags runs, as
     {fwd, bwd: a name of RENDER_FAMILIES; rec, s16, g16, chain, dec_fused: bool}.  Host only: no GPU is needed."""
     out = (ctypes.c_int * 8)()
-    check(lib().spair_step_plan(ctypes.byref(dims), ctypes.c_void_p(int(workspace)), int(flags), out), "spair_step_plan")
+    check(lib().spair_step_plan(ctypes.byref(dims), int(workspace), int(flags), 0, out, 8), "spair_step_plan")
     return dict(fwd=RENDER_FAMILIES[out[0]], bwd=RENDER_FAMILIES[out[1]], rec=bool(out[2]), s16=bool(out[3]), g16=bool(out[4]),
                 chain=bool(out[5]), dec_fused=bool(out[6]))
 
@@ -76,13 +116,13 @@ STEP_PLAN_INTS = 38                                            # SPAIR_STEP_PLAN
 
 
 def step_plan_n(dims, workspace, flags=0, input_grad=False):
-    """spair_step_plan_n: the rest of the plan step_plan reports, for a step with these SpairDims, workspace address, SpairStep.flags and
+    """spair_step_plan: the rest of the plan step_plan reports, for a step with these SpairDims, workspace address, SpairStep.flags and
     (backward) image gradient, as {side, dec_dgrad_fused, dec_wgrad_grouped, dec_wgrad_late: bool; pw0: first layer of the fused 1x1 stack
     (n_conv + 1: none); stem: where the stem's weight gradient is taken, a name of STEM_WGRADS; fwd, dgrad: per backbone layer 1 .. n_conv
     (conv_out last) a name of CONV_KERNELS; gate_bits: per layer, whether its data gradient reads the sign bits the layer below left}."""
     out = (ctypes.c_int * STEP_PLAN_INTS)()
-    check(lib().spair_step_plan_n(ctypes.byref(dims), ctypes.c_void_p(int(workspace)), int(flags), int(bool(input_grad)), out, STEP_PLAN_INTS),
-          "spair_step_plan_n")
+    check(lib().spair_step_plan(ctypes.byref(dims), int(workspace), int(flags), int(bool(input_grad)), out, STEP_PLAN_INTS),
+          "spair_step_plan")
     layers = range(dims.n_conv)
     return dict(side=bool(out[8]), dec_dgrad_fused=bool(out[9]), dec_wgrad_grouped=bool(out[10]), dec_wgrad_late=bool(out[11]), pw0=out[12],
                 stem=STEM_WGRADS[out[13]], fwd=tuple(CONV_KERNELS[out[14 + i]] for i in layers),

@@ -19,7 +19,7 @@ int conv_s2k4_patch_dgrad16(const void* dout, const void* const* wd, const void*
                             int s_, const float* stem_xp, int stem_hin, int stem_s, float* stem_part, long long stem_part_cap, float* stem_dw,
                             float* stem_db, hipStream_t s, const void* gate_bits = nullptr);
 
-// The training step's plan names (engine.hip, plan_step; reported by spair_step_plan_n).  A backbone layer's forward or data-gradient kernel: one
+// The training step's plan names (engine.hip, plan_step; reported by spair_step_plan).  A backbone layer's forward or data-gradient kernel: one
 // implicit-GEMM launch in the step's dtype (a strided data gradient: all output-parity classes in it), the patch-resident kernel, one launch per
 // output-parity class, or the fused trailing 1x1 stack (pointwise.hip)
 enum ConvKernel { CONV_GEMM = SPAIR_CONV_GEMM, CONV_PATCH = SPAIR_CONV_PATCH, CONV_PER_CLASS = SPAIR_CONV_PER_CLASS, CONV_PW_STACK = SPAIR_CONV_PW_STACK };

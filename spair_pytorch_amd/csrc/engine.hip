@@ -137,7 +137,7 @@ static int validate(const SpairDims& d) {
 // base's 16-byte alignment -- every buffer carve() hands out sits a multiple of 256 bytes past the base, so the base stands for the sprites,
 // records and d-logits the renderer's predicates test.  make_ctx plans the step, carve() the workspace (flags 0, no image gradient, an aligned
 // base: flags, the image gradient and a misaligned base only ever turn kernels off, so what any step plan reads the workspace has), and the
-// spair_step_plan diagnostics report it.  input_grad (spair_backward_x): the image gradient reads d act0 from HBM, so the stem's weight
+// spair_step_plan diagnostic reports it.  input_grad (SpairStepIO.grad_x): the image gradient reads d act0 from HBM, so the stem's weight
 // gradient is not fused into conv_1's data gradient.
 // A rectangular image (Iw != I, or a rectangular padded frame) refuses every square-only kernel here, in the plan, whatever their _supported
 // predicates (most of which only see I) say: the fused chain, the records / matrix-core / second-generation renderer (render_plan), the
@@ -761,16 +761,17 @@ static GemmNT dgrad_classes16(const Ctx& c, int i) {
     return g;
 }
 
-static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
-                    const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace, void* stream, bool input_grad = false) {
-    if (!d || !st || !params || !x || !workspace) return SPAIR_ERR_SHAPE;
+// what both directions share: the buffers they both read (checked here, once), the normalised dims, their layouts and the step plan
+static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const SpairStepIO* io, void* stream, bool input_grad = false) {
+    if (!d || !st || !io || !io->params || !io->x || !io->eps_box || !io->eps_attr || !io->eps_depth || !io->u_pres || !io->workspace)
+        return SPAIR_ERR_SHAPE;
     c.d = spair_dims_norm(*d); c.st = *st;
     TRY(validate(c.d));
     d = &c.d;
     c.L = make_cell_layout(*d);
     c.PL = make_param_layout(*d);
-    c.w = carve(*d, workspace);
-    c.params = params; c.x = x; c.s = (hipStream_t)stream; c.tn_part = c.w.tn_part;
+    c.w = carve(*d, io->workspace);
+    c.params = io->params; c.x = io->x; c.s = (hipStream_t)stream; c.tn_part = c.w.tn_part;
     CellHyper& H = c.H;
     H.wheel = st->wheel; H.kl_scale = st->kl_scale * d->vae_beta; H.img = (float)d->I; H.anchor = d->anchor;
     H.cell_over_img = (float)((double)d->cell_px / (double)d->I);
@@ -780,10 +781,10 @@ static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const float
     H.range_yx = d->max_yx - d->min_yx; H.range_hw = d->max_hw - d->min_hw;
     for (int i = 0; i < 6; ++i) { H.prior_mean[i] = d->prior_mean[i]; H.prior_std[i] = d->prior_std[i]; }
     H.count_prior_prob = st->count_prior_prob;
-    c.w.cb.edge = params + c.PL.edge;
-    c.w.cb.eps_box = eps_box; c.w.cb.eps_attr = eps_attr; c.w.cb.eps_depth = eps_depth; c.w.cb.u_pres = u_pres;
+    c.w.cb.edge = c.params + c.PL.edge;
+    c.w.cb.eps_box = io->eps_box; c.w.cb.eps_attr = io->eps_attr; c.w.cb.eps_depth = io->eps_depth; c.w.cb.u_pres = io->u_pres;
     fill_diag(c);
-    static_cast<StepPlan&>(c) = plan_step(*d, st->flags, input_grad, workspace);
+    static_cast<StepPlan&>(c) = plan_step(*d, st->flags, input_grad, io->workspace);
     c.rg = render_geom(*d, c.L, &c.w.cb);
     return SPAIR_OK;
 }
@@ -1140,22 +1141,14 @@ static int cells_fwd(Ctx& c) {
     return SPAIR_OK;
 }
 
-extern "C" int spair_forward(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
-                             const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace, float* loss_out,
-                             float* recon, float* z_where, float* z_pres, void* stream) {
-    return spair_forward_out(d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, loss_out, recon, z_where, z_pres, stream, nullptr);
-}
-
-extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
-                                 const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace, float* loss_out,
-                                 float* recon, float* z_where, float* z_pres, void* stream, float* inv_den) {
+extern "C" int spair_forward(const SpairDims* d, const SpairStep* st, const SpairStepIO* io, void* stream) {
     Ctx c;
-    TRY(make_ctx(c, d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, stream));
+    TRY(make_ctx(c, d, st, io, stream));
     d = &c.d;      // normalised (spair_dims_norm)
-    if (!loss_out || !recon || !z_where || !z_pres || !eps_box || !eps_attr || !eps_depth || !u_pres) return SPAIR_ERR_SHAPE;
+    if (!io->loss_out || !io->recon || !io->z_where || !io->z_pres) return SPAIR_ERR_SHAPE;
     const CellLayout& L = c.L;
     CellBufs& P = c.w.cb;
-    P.z_where = z_where; P.z_pres = z_pres;
+    P.z_where = io->z_where; P.z_pres = io->z_pres;
     SideStream* side = nullptr;
     if (c.use_side) TRY(side_stream(side));
     std::unique_lock<std::mutex> enq_lock;
@@ -1169,14 +1162,13 @@ extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const 
             if (side && hipEventRecord(side->ev[3], side->s) != hipSuccess) return SPAIR_ERR_LAUNCH;
             TRY(cells_init_tables(d->G, d->Gw, c.L.LB, c.w.cell_h, c.w.cell_w, c.w.cidx, c.w.nbr, c.w.cons, c.w.diag_start, c.s));
             if (st->draw_noise)
-                TRY(spair_noise_fill(d, st->noise_seed, const_cast<float*>(eps_box), const_cast<float*>(eps_attr), const_cast<float*>(eps_depth),
-                                     const_cast<float*>(u_pres), c.s));
+                TRY(spair_noise_fill(d, st->noise_seed, io->eps_box, io->eps_attr, io->eps_depth, io->u_pres, c.s));
             TRY(prep_weights(c, st->train != 0, 1));
         }
         if (side && hipEventRecord(side->ev[4], side->s) != hipSuccess) return SPAIR_ERR_LAUNCH;
         // the padded copy is only read by the stem's weight gradient: it stays behind the event conv_1 waits on (the helper stream's
         // later joins order it before the backward)
-        if (c.stem_unpadded) TRY(misc_pad_input(x, c.w.xpad, d->B, d->C, d->I, d->Iw, d->pad_pre, c.PL.conv[0].hin, c.PL.conv[0].win, c.s));
+        if (c.stem_unpadded) TRY(misc_pad_input(c.x, c.w.xpad, d->B, d->C, d->I, d->Iw, d->pad_pre, c.PL.conv[0].hin, c.PL.conv[0].win, c.s));
     }
     const int ps_bb = prof_begin(PS_BACKBONE_FWD, c.s);
     TRY(backbone_stem_fwd(c));
@@ -1214,23 +1206,23 @@ extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const 
         } else if (c.use_dec_fused) {
             // all three layers + the sprite epilogue in one activation-stationary launch (dec_fused.hip)
             ProfScope p2(PS_DEC2_FWD, c.s);
-            TRY(dec_fused_fwd(c.w.Za16, L.ld_rec, c.w.dec_stream, params + PL.lin[LIN_DEC0].b, params + PL.lin[LIN_DEC1].b, params + PL.lin[LIN_DEC2].b,
+            TRY(dec_fused_fwd(c.w.Za16, L.ld_rec, c.w.dec_stream, c.params + PL.lin[LIN_DEC0].b, c.params + PL.lin[LIN_DEC1].b, c.params + PL.lin[LIN_DEC2].b,
                               c.w.Hd1, c.w.Hd2, c.w.S, c.w.ld_s, N, d->A, per, d->obj_logit_scale, d->alpha_logit_scale, d->alpha_logit_bias, c.s));
         } else {
         if (b16) {   // hidden activations stored as bf16
-            TRY(nt16(c, c.w.Za16, L.ld_rec, c.w.lin_wf[LIN_DEC0], K0, c.w.Hd1, SP_DEC_H1, 1, N, SP_DEC_H1, K0, params + PL.lin[LIN_DEC0].b, nullptr, 0, 1));
+            TRY(nt16(c, c.w.Za16, L.ld_rec, c.w.lin_wf[LIN_DEC0], K0, c.w.Hd1, SP_DEC_H1, 1, N, SP_DEC_H1, K0, c.params + PL.lin[LIN_DEC0].b, nullptr, 0, 1));
             TRY(nt16(c, c.w.Hd1, SP_DEC_H1, c.w.lin_wf[LIN_DEC1], SP_DEC_H1, c.w.Hd2, SP_DEC_H2, 1, N, SP_DEC_H2, SP_DEC_H1,
-                     params + PL.lin[LIN_DEC1].b, nullptr, 0, 1));
+                     c.params + PL.lin[LIN_DEC1].b, nullptr, 0, 1));
         } else {
-            TRY(fwd_lin(c, LIN_DEC0, c.w.Za, L.ld_rec, c.w.Hd1, SP_DEC_H1, 0, N, params + PL.lin[LIN_DEC0].b, SP_DEC_H1, 1));
-            TRY(fwd_lin(c, LIN_DEC1, c.w.Hd1, SP_DEC_H1, c.w.Hd2, SP_DEC_H2, 0, N, params + PL.lin[LIN_DEC1].b, SP_DEC_H2, 1));
+            TRY(fwd_lin(c, LIN_DEC0, c.w.Za, L.ld_rec, c.w.Hd1, SP_DEC_H1, 0, N, c.params + PL.lin[LIN_DEC0].b, SP_DEC_H1, 1));
+            TRY(fwd_lin(c, LIN_DEC1, c.w.Hd1, SP_DEC_H1, c.w.Hd2, SP_DEC_H2, 0, N, c.params + PL.lin[LIN_DEC1].b, SP_DEC_H2, 1));
         }
         {   // decoder.out with the sprite sigmoid epilogue fused (models.py:485-492)
             ProfScope p2(PS_DEC2_FWD, c.s);
             GemmNT g;
             memset(&g, 0, sizeof(g));
             g.A = c.w.Hd2; g.lda = SP_DEC_H2; g.B = c.w.lin_wf[LIN_DEC2]; g.ldb = K2; g.C = c.w.S; g.ldc = c.w.ld_s; g.M = N; g.N = per; g.K = K2;
-            g.bias = params + PL.lin[LIN_DEC2].b; g.sprite_ch = d->C + 1;
+            g.bias = c.params + PL.lin[LIN_DEC2].b; g.sprite_ch = d->C + 1;
             g.c_bf16 = c.rp.s16;      // bf16 step: the sprites leave as 16-bit (grey, alpha) pairs -- half the bytes for the renderer, both
                                       // ways (colour images: fp32 sprites for the generic-channel renderer)
             g.obj_scale = d->obj_logit_scale; g.alpha_scale = d->alpha_logit_scale; g.alpha_bias = d->alpha_logit_bias;
@@ -1243,15 +1235,15 @@ extern "C" int spair_forward_out(const SpairDims* d, const SpairStep* st, const 
     {
         ProfScope ps(PS_RENDER_FWD, c.s);
         float* const aux = st->train ? c.w.aux : nullptr;
-        if (c.rp.fwd == RENDER_MMA) TRY(render_fwd_mma(c.rg, c.w.S, c.w.ld_s, c.w.rrec, x, recon, aux, c.w.bce_partial, inv_den, c.s));
-        else if (c.rp.fwd == RENDER_GEN2) TRY(render_fwd2(c.rg, c.w.S, c.w.ld_s, c.rp.s16, x, recon, aux, c.w.bce_partial, inv_den, c.s));
-        else if (c.rp.fwd == RENDER_GEN1) TRY(render_fwd1(c.rg, c.w.S, c.w.ld_s, c.rp.s16, x, recon, aux, c.w.bce_partial, inv_den, c.s));
-        else TRY(render_fwd_c(c.rg, c.w.S, c.w.ld_s, d->C, x, recon, aux, c.w.bce_partial, inv_den, c.s));
+        if (c.rp.fwd == RENDER_MMA) TRY(render_fwd_mma(c.rg, c.w.S, c.w.ld_s, c.w.rrec, c.x, io->recon, aux, c.w.bce_partial, io->inv_den, c.s));
+        else if (c.rp.fwd == RENDER_GEN2) TRY(render_fwd2(c.rg, c.w.S, c.w.ld_s, c.rp.s16, c.x, io->recon, aux, c.w.bce_partial, io->inv_den, c.s));
+        else if (c.rp.fwd == RENDER_GEN1) TRY(render_fwd1(c.rg, c.w.S, c.w.ld_s, c.rp.s16, c.x, io->recon, aux, c.w.bce_partial, io->inv_den, c.s));
+        else TRY(render_fwd_c(c.rg, c.w.S, c.w.ld_s, d->C, c.x, io->recon, aux, c.w.bce_partial, io->inv_den, c.s));
     }
     if (side && hipStreamWaitEvent(c.s, side->ev[1], 0) != hipSuccess) return SPAIR_ERR_LAUNCH;
     ProfScope psl(PS_LOSS, c.s);
     TRY(loss_finalize(c.w.bce_partial, render_num_blocks(d->B, d->I, d->Iw), c.w.kl_partial, loss_gauss_kl_blocks(L), c.w.klp, d->B,
-                      st->kl_scale, d->vae_beta, loss_out,
+                      st->kl_scale, d->vae_beta, io->loss_out,
                       c.use_chain && c.w.chain_sync ? c.w.chain_sync + CHAIN_SYNC_STICKY(d->B, chain_bands(*d)) : nullptr, st->status,
                       st->status_host, c.s));
     return SPAIR_OK;
@@ -1393,23 +1385,6 @@ static int decoder_wgrads16(Ctx& c, float* grads, void* ev_decoder) {
     return record_ready(ev_decoder, c.s);
 }
 
-extern "C" int spair_backward_ev(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
-                                 const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace,
-                                 const float* grad_loss, float* grads, void* stream, void* ev_decoder, void* ev_cells, void* ev_backbone);
-
-extern "C" int spair_backward(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
-                              const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace,
-                              const float* grad_loss, float* grads, void* stream) {
-    return spair_backward_ev(d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, grad_loss, grads, stream, nullptr, nullptr, nullptr);
-}
-
-extern "C" int spair_backward_ev(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
-                                 const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace,
-                                 const float* grad_loss, float* grads, void* stream, void* ev_decoder, void* ev_cells, void* ev_backbone) {
-    return spair_backward_out(d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, grad_loss, grads, stream, ev_decoder, ev_cells,
-                              ev_backbone, nullptr, nullptr, nullptr, nullptr, nullptr);
-}
-
 int input_grad_glimpse(const float* nbox, int B, int ncell, const float* dgl, int ld, float* out, int C, int I, int Iw, int P, int ac, hipStream_t s);
 int input_grad_stem(const void* dact, int dact_bf16, const float* w, int B, int C, int I, int Iw, int pre, int k, int s, int Hout, int Wout, int Cout,
                     const float* add, const float* aux, const float* bce_g, float* grad_x, hipStream_t st);
@@ -1421,20 +1396,18 @@ extern "C" int64_t spair_input_grad_scratch_bytes(const SpairDims* d0) {
     return ((int64_t)d->B * d->C * d->I * d->Iw * 4 + 255) & ~(int64_t)255;      // dx_gl [B][C][I][Iw] fp32
 }
 
-// grad_x == nullptr: exactly spair_backward_out.  Otherwise, once the parameter gradients are complete (after ev_backbone), the image
-// gradient: [chain] dGl = dHe1 W_enc0, the glimpse adjoint into x_scratch, then the stem's data gradient, whose epilogue writes grad_x
-static int backward_impl(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
-                         const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace,
-                         const float* grad_loss, float* grads, void* stream, void* ev_decoder, void* ev_cells, void* ev_backbone,
-                         const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
-                         float* aux_scratch, float* grad_x, int bce_target, float* x_scratch) {
+// With grad_x, once the parameter gradients are complete (after ev_backbone), the image gradient: [chain] dGl = dHe1 W_enc0, the glimpse
+// adjoint into x_scratch, then the stem's data gradient, whose epilogue writes grad_x
+extern "C" int spair_backward(const SpairDims* d, const SpairStep* st, const SpairStepIO* io, void* stream) {
     Ctx c;
-    TRY(make_ctx(c, d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, stream, grad_x != nullptr));
+    TRY(make_ctx(c, d, st, io, stream, io && io->grad_x));
     d = &c.d;      // normalised (spair_dims_norm)
+    const float* const grad_loss = io->grad_loss;
+    float* const grads = io->grads;
     if (!grad_loss || !grads) return SPAIR_ERR_SHAPE;
-    if (grad_recon && (!inv_den || !aux_scratch)) return SPAIR_ERR_SHAPE;
-    if (grad_x && (!x_scratch || c.PL.n_conv < 2)) return grad_x && !x_scratch ? SPAIR_ERR_SHAPE : SPAIR_ERR_UNSUPPORTED;
-    if (grad_x && (size_t)c.PL.conv[0].cout * d->C * c.PL.conv[0].k * c.PL.conv[0].k * 4 > 65536) return SPAIR_ERR_UNSUPPORTED;
+    if (io->grad_recon && (!io->inv_den || !io->aux_scratch)) return SPAIR_ERR_SHAPE;
+    if (io->grad_x && (!io->x_scratch || c.PL.n_conv < 2)) return !io->x_scratch ? SPAIR_ERR_SHAPE : SPAIR_ERR_UNSUPPORTED;
+    if (io->grad_x && (size_t)c.PL.conv[0].cout * d->C * c.PL.conv[0].k * c.PL.conv[0].k * 4 > 65536) return SPAIR_ERR_UNSUPPORTED;
     const CellLayout& L = c.L;
     CellBufs& P = c.w.cb;
     const ParamLayout& PL = c.PL;
@@ -1447,11 +1420,11 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
     // and P.gloss (the KL terms' scale further down) stay as they are
     const float* r_aux = c.w.aux;
     const float* r_gloss = grad_loss;
-    if (grad_recon) {
+    if (io->grad_recon) {
         const size_t n2 = (size_t)d->B * d->C * d->I * d->Iw * 2;
-        TRY(outgrad_recon_fold(c.w.aux, grad_loss, grad_recon, inv_den, aux_scratch, aux_scratch + n2, d->B, d->C, d->I, d->Iw, c.s));
-        r_aux = aux_scratch;
-        r_gloss = aux_scratch + n2;
+        TRY(outgrad_recon_fold(c.w.aux, grad_loss, io->grad_recon, io->inv_den, io->aux_scratch, io->aux_scratch + n2, d->B, d->C, d->I, d->Iw, c.s));
+        r_aux = io->aux_scratch;
+        r_gloss = io->aux_scratch + n2;
     }
     {
         ProfScope ps(PS_RENDER_BWD, c.s);
@@ -1465,7 +1438,7 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
         else TRY(render_bwd_c(c.rg, c.w.S, c.w.ld_s, d->C, r_aux, r_gloss, c.w.dLog, P.g_nbox_r, P.g_pres_r, P.g_depth_r, c.w.ld_s, so, sa, c.s));
     }
     // adjoints of the z_where / z_pres outputs: added to the rows the renderer just wrote, before the per-cell backward reads them
-    TRY(outgrad_rows_fold(P.cell_h, P.cell_w, d->B, d->G, d->Gw, grad_z_where, grad_z_pres, P.g_nbox_r, P.g_pres_r, c.s));
+    TRY(outgrad_rows_fold(P.cell_h, P.cell_w, d->B, d->G, d->Gw, io->grad_z_where, io->grad_z_pres, P.g_nbox_r, P.g_pres_r, c.s));
     SideStream* side = nullptr;
     if (c.use_side) TRY(side_stream(side));
     std::unique_lock<std::mutex> enq_lock;
@@ -1473,7 +1446,7 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
     if (PL.oc_n) {
         ProfScope ps(PS_DECODER_BWD, c.s);
         TRY(oc_decoder_bwd(c, grads));
-        TRY(record_ready(ev_decoder, c.s));
+        TRY(record_ready(io->ev_decoder, c.s));
     } else if (b16) {   // decoder, bf16-stored activations and gradients: the data-gradient chain stays on the caller's stream, the three
                  // weight gradients go to the helper stream and overlap with the (latency-bound) per-cell backward chain
         const LinSpec& l0 = PL.lin[LIN_DEC0];
@@ -1496,7 +1469,7 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
         if (!c.dec_wgrad_late) {      // no helper stream / per-wavefront launches: the weight gradients right here
             if (side) TRY(stream_link(c.s, side->s, side->ev[0]));
             OnHelper on_helper(c, side);
-            TRY(decoder_wgrads16(c, grads, ev_decoder));
+            TRY(decoder_wgrads16(c, grads, io->ev_decoder));
         }
     } else {   // decoder
         ProfScope ps(PS_DECODER_BWD, c.s);
@@ -1506,7 +1479,7 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
         TRY(bwd_lin(c, LIN_DEC1, SP_DEC_H2, c.w.dHd2, SP_DEC_H2, c.w.dHd1, SP_DEC_H1, 0, N, c.w.Hd1, SP_DEC_H1));
         TRY(wgrad_lin(c, LIN_DEC0, c.w.dHd1, SP_DEC_H1, c.w.Za, L.ld_rec, grads, N));
         TRY(bwd_lin(c, LIN_DEC0, SP_DEC_H1, c.w.dHd1, SP_DEC_H1, P.g_attr_r, L.ld_rec, 0, N, nullptr, 0));
-        TRY(record_ready(ev_decoder, c.s));
+        TRY(record_ready(io->ev_decoder, c.s));
     }
     // per-cell chain, reverse wavefront order
     const int ps_cells = prof_begin(PS_CELLS_BWD, c.s);
@@ -1517,9 +1490,9 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
         memset(&a, 0, sizeof(a));
         a.L = L; a.P = P; a.H = c.H;
         for (int i = 0; i < CW_COUNT; ++i) a.wt[i] = reinterpret_cast<const uint4*>(c.w.chain_wt[i]);
-        a.w_obj2 = params + PL.lin[LIN_OBJ2].w;
+        a.w_obj2 = c.params + PL.lin[LIN_OBJ2].w;
         a.gedge = grads + PL.edge; a.gedge_part = c.w.gedge_part;
-        a.x = x; a.I = d->I; a.Pp = d->P; a.ac = d->align_corners;
+        a.x = c.x; a.I = d->I; a.Pp = d->P; a.ac = d->align_corners;
         a.stamps = (st->flags & 2) ? c.w.stamps : nullptr;
         a.nbands = chain_bands(*d); a.sync = c.w.chain_sync; a.bnd_rec = c.w.bnd_rec; a.bnd_grad = c.w.bnd_grad;
         TRY(chain_bwd(a, c.s));
@@ -1542,7 +1515,7 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
         TRY(bwd_lin(c, LIN_ENC1, SP_ENC_H2, P.dHe2, SP_ENC_H2, P.dHe1, SP_ENC_H1, r0, R, P.He1, SP_ENC_H1));
         TRY(bwd_lin(c, LIN_ENC0, SP_ENC_H1, P.dHe1, SP_ENC_H1, P.dGl, L.ld_gl, r0, R, nullptr, 0));
         }
-        TRY(stn_glimpse_bwd(x, P.nbox, L.B, P.dGl, L.ld_gl, P.g_nbox_stn, r0, R, d->C, d->I, d->Iw, d->P, d->align_corners, chain_image_fp16(*d),
+        TRY(stn_glimpse_bwd(c.x, P.nbox, L.B, P.dGl, L.ld_gl, P.g_nbox_stn, r0, R, d->C, d->I, d->Iw, d->P, d->align_corners, chain_image_fp16(*d),
                             c.s));
         TRY(cells_bwd_box(L, P, c.H, r0, R, c.s));
         TRY(bwd_lin(c, LIN_BOXH1, L.NP + 8, P.dOb, L.ld_ob, P.dHb2, SP_LDH, r0, R, P.Hb2, SP_LDH));
@@ -1555,7 +1528,7 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
     {   // the per-cell weight gradients (helper stream) and the backbone backward (caller's stream) both hang off the chain only
         if (side) TRY(stream_link(c.s, side->s, side->ev[2]));
         OnHelper on_helper(c, side);
-        if (c.dec_wgrad_late) TRY(decoder_wgrads16(c, grads, ev_decoder));      // (see decoder_wgrads16)
+        if (c.dec_wgrad_late) TRY(decoder_wgrads16(c, grads, io->ev_decoder));      // (see decoder_wgrads16)
         const int ps_wg = prof_begin(PS_CELLS_WGRAD, c.s);
         // weight gradients of the per-cell nets: long-K GEMMs over all N rows
         if (c.use_chain) {
@@ -1581,44 +1554,26 @@ static int backward_impl(const SpairDims* d, const SpairStep* st, const float* p
         TRY(wgrad_lin(c, LIN_OBJ2, P.dOo, L.ld_oo, P.Ho2, SP_LDH, grads, N));
         }
         prof_end(ps_wg, c.s);
-        TRY(record_ready(ev_cells, c.s));
+        TRY(record_ready(io->ev_cells, c.s));
         if (side && hipEventRecord(side->ev[3], side->s) != hipSuccess) return SPAIR_ERR_LAUNCH;
     }
     { ProfScope ps(PS_BACKBONE_BWD, c.s); TRY(backbone_bwd(c, grads)); }
     if (side && hipStreamWaitEvent(c.s, side->ev[3], 0) != hipSuccess) return SPAIR_ERR_LAUNCH;      // join
-    TRY(record_ready(ev_backbone, c.s));
-    if (grad_x) {     // behind ev_backbone: the gradient buckets are not delayed
+    TRY(record_ready(io->ev_backbone, c.s));
+    if (io->grad_x) {     // behind ev_backbone: the gradient buckets are not delayed
         if (c.use_chain) {      // the fused chain keeps dHe1 (bf16) but not dGl: one 16-bit NT GEMM, as bwd_lin does per wavefront
             const LinSpec& e0 = PL.lin[LIN_ENC0];
             const int K = round_up(e0.out, 8);
             TRY(nt16(c, P.dHe1, SP_ENC_H1, c.w.lin_wt[LIN_ENC0], K, P.dGl, L.ld_gl, 0, N, e0.in, K, nullptr, nullptr, 0, 0));
         }
+        float* const x_scratch = static_cast<float*>(io->x_scratch);
         TRY(input_grad_glimpse(P.nbox, d->B, d->G * d->Gw, P.dGl, L.ld_gl, x_scratch, d->C, d->I, d->Iw, d->P, d->align_corners, c.s));
         const ConvSpec& c0 = PL.conv[0];
-        TRY(input_grad_stem(c.w.dact[0], b16, params + c0.w, d->B, d->C, d->I, d->Iw, d->pad_pre, c0.k, c0.s, c0.hout, c0.wout, c0.cout, x_scratch,
+        TRY(input_grad_stem(c.w.dact[0], b16, c.params + c0.w, d->B, d->C, d->I, d->Iw, d->pad_pre, c0.k, c0.s, c0.hout, c0.wout, c0.cout, x_scratch,
                             c.w.aux,
-                            bce_target ? grad_loss : nullptr, grad_x, c.s));
+                            io->bce_target ? grad_loss : nullptr, io->grad_x, c.s));
     }
     return SPAIR_OK;
-}
-
-extern "C" int spair_backward_out(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
-                                  const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace,
-                                  const float* grad_loss, float* grads, void* stream, void* ev_decoder, void* ev_cells, void* ev_backbone,
-                                  const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
-                                  float* aux_scratch) {
-    return backward_impl(d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, grad_loss, grads, stream, ev_decoder, ev_cells,
-                         ev_backbone, inv_den, grad_recon, grad_z_where, grad_z_pres, aux_scratch, nullptr, 0, nullptr);
-}
-
-extern "C" int spair_backward_x(const SpairDims* d, const SpairStep* st, const float* params, const float* x, const float* eps_box,
-                                const float* eps_attr, const float* eps_depth, const float* u_pres, void* workspace,
-                                const float* grad_loss, float* grads, void* stream, void* ev_decoder, void* ev_cells, void* ev_backbone,
-                                const float* inv_den, const float* grad_recon, const float* grad_z_where, const float* grad_z_pres,
-                                float* aux_scratch, float* grad_x, int bce_target, void* x_scratch) {
-    return backward_impl(d, st, params, x, eps_box, eps_attr, eps_depth, u_pres, workspace, grad_loss, grads, stream, ev_decoder, ev_cells,
-                         ev_backbone, inv_den, grad_recon, grad_z_where, grad_z_pres, aux_scratch, grad_x, bce_target,
-                         reinterpret_cast<float*>(x_scratch));
 }
 
 // diagnostic: copy the forward chain kernel's stage stamps (SpairStep.flags bit 1) into a caller buffer of n uint64
@@ -1633,10 +1588,10 @@ extern "C" int spair_chain_stamps(const SpairDims* d0, const void* workspace, un
 
 static_assert(SPAIR_RENDER_MMA == RENDER_MMA && SPAIR_RENDER_GEN2 == RENDER_GEN2 && SPAIR_RENDER_GEN1 == RENDER_GEN1 &&
               SPAIR_RENDER_COLOUR == RENDER_COLOUR, "include/spair_hip.h names the RenderFamily values");
-static_assert(SPAIR_STEP_PLAN_INTS == 14 + 3 * SP_MAX_CONV, "include/spair_hip.h lays out spair_step_plan_n");
+static_assert(SPAIR_STEP_PLAN_INTS == 14 + 3 * SP_MAX_CONV, "include/spair_hip.h lays out spair_step_plan");
 // diagnostic: the kernel plan make_ctx computes for these dims, workspace alignment, SpairStep.flags and input gradient (host only: nothing
 // launched, nothing read)
-extern "C" int spair_step_plan_n(const SpairDims* d0, const void* workspace, int flags, int input_grad, int* out, int n) {
+extern "C" int spair_step_plan(const SpairDims* d0, const void* workspace, int flags, int input_grad, int* out, int n) {
     if (!d0 || !workspace || !out) return SPAIR_ERR_SHAPE;
     const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
     TRY(validate(*d));
@@ -1649,9 +1604,6 @@ extern "C" int spair_step_plan_n(const SpairDims* d0, const void* workspace, int
     }
     for (int i = 0; i < std::min(n, SPAIR_STEP_PLAN_INTS); ++i) out[i] = v[i];
     return SPAIR_OK;
-}
-extern "C" int spair_step_plan(const SpairDims* d, const void* workspace, int flags, int* out) {
-    return spair_step_plan_n(d, workspace, flags, 0, out, 8);
 }
 
 // ---- workspace view (diagnostic) -----------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-// Gradient of the training step with respect to its input image (spair_backward_x).  In the reference the image reaches the loss three ways:
+// Gradient of the training step with respect to its input image (SpairStepIO.grad_x).  In the reference the image reaches the loss three ways:
 // the backbone, the glimpse STN (border padding) and the BCE target.  Two kernels, both plain gathers with a fixed summation order (no
 // atomics, so grad_x is bit-for-bit repeatable):
 //  * k_glimpse_adjoint: dx_gl[b] = sum over the cells n of sample b of Wy_n^T dG_n Wx_n per channel -- the transpose of the forward glimpse

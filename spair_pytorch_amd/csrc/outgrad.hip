@@ -1,4 +1,4 @@
-// Adjoints of the step's three map outputs (recon, z_where, z_pres) folded into the hand-written backward (spair_backward_out).
+// Adjoints of the step's three map outputs folded into the hand-written backward (SpairStepIO.grad_recon, grad_z_where, grad_z_pres).
 //
 // The reference returns all three as live autograd tensors (models.py:35-131), so a user term on any of them trains through the
 // whole model.  Every engine path shares the entry points these kernels feed, so they are the whole feature:

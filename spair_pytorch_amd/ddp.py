@@ -9,7 +9,7 @@ back-propagates  BCE_sum_local + KL_sum_local / (B_local * S)  and the gradients
 plain DDP averaging would silently divide the reconstruction gradient by S.  The model does this
 when ``world_size`` is set; ``global_loss`` rebuilds the reported ELBO the same way.
 
-Overlap: ``spair_backward_ev`` (include/spair_hip.h) records one event per gradient range as soon as
+Overlap: ``spair_backward`` (include/spair_hip.h, ``SpairStepIO.ev_*``) records one event per gradient range as soon as
 that range is final -- decoder first (its weight gradients run on the engine's helper stream under
 the per-cell backward chain), then the box / encoder / z / obj nets, last the backbone with the edge
 element.  ``allreduce_gradients(model)`` makes a communication stream wait on each event and starts

@@ -13,8 +13,8 @@ step, train.py:64-67) runs unchanged.  All arithmetic of the step is in libspair
   enqueues ``spair_backward`` (hand-written reverse pass) which accumulates into ``p.grad``;
 * with ``differentiable_outputs=True`` the recon / z_where / z_pres outputs are autograd tensors
   too, as in the reference: adjoints that reach them are folded into that same reverse pass
-  (``spair_forward_out`` / ``spair_backward_out``);
-* an input ``x`` that requires grad gets the reference's ``x.grad`` (``spair_backward_x``): the
+  (``SpairStepIO.inv_den`` / ``grad_recon`` / ``grad_z_where`` / ``grad_z_pres``);
+* an input ``x`` that requires grad gets the reference's ``x.grad`` (``SpairStepIO.grad_x``): the
   backbone, glimpse and BCE-target terms.  As in torch, the BCE-target term is ``-logit(recon)``
   unclamped: ``x.grad`` is +inf wherever recon is exactly 0 (-inf where it is exactly 1);
 * there is no PyTorch/CPU fallback: without the HIP library or a GPU this module raises.
@@ -30,32 +30,11 @@ from torch import nn
 
 from . import _lib as L
 from . import config as cfg
+from ._lib import SpairDims, SpairStep  # noqa: F401  (the C structs' mirrors; exported here as before)
 from .modules import Backbone, ObjectConvDecoder, ObjectConvEncoder, build_MLP, exponential_decay
 
 DIST_NAMES = ['cy_logit', 'cx_logit', 'height_logit', 'width_logit', 'attr', 'depth_logit']
-
-
-class SpairDims(ctypes.Structure):
-    """include/spair_hip.h :: SpairDims"""
-    _fields_ = [("B", ctypes.c_int), ("C", ctypes.c_int), ("I", ctypes.c_int), ("G", ctypes.c_int),
-                ("P", ctypes.c_int), ("A", ctypes.c_int), ("F", ctypes.c_int), ("NP", ctypes.c_int),
-                ("n_conv", ctypes.c_int), ("conv_k", ctypes.c_int * 8), ("conv_s", ctypes.c_int * 8),
-                ("conv_c", ctypes.c_int * 8), ("pad_pre", ctypes.c_int), ("pad_post", ctypes.c_int),
-                ("cell_px", ctypes.c_int), ("dtype", ctypes.c_int), ("align_corners", ctypes.c_int),
-                ("anchor", ctypes.c_float), ("max_yx", ctypes.c_float), ("min_yx", ctypes.c_float),
-                ("max_hw", ctypes.c_float), ("min_hw", ctypes.c_float), ("obj_logit_scale", ctypes.c_float),
-                ("alpha_logit_scale", ctypes.c_float), ("alpha_logit_bias", ctypes.c_float),
-                ("vae_beta", ctypes.c_float), ("prior_mean", ctypes.c_float * 6), ("prior_std", ctypes.c_float * 6),
-                ("obj_conv", ctypes.c_int), ("oc_n", ctypes.c_int), ("oc_k", ctypes.c_int * 4), ("oc_s", ctypes.c_int * 4),
-                ("oc_c", ctypes.c_int * 4), ("lookback", ctypes.c_int),
-                ("Iw", ctypes.c_int), ("Gw", ctypes.c_int), ("pad_post_w", ctypes.c_int)]
-
-
-class SpairStep(ctypes.Structure):
-    """include/spair_hip.h :: SpairStep"""
-    _fields_ = [("wheel", ctypes.c_float), ("count_prior_prob", ctypes.c_float), ("kl_scale", ctypes.c_float),
-                ("train", ctypes.c_int), ("flags", ctypes.c_int), ("draw_noise", ctypes.c_int), ("noise_seed", ctypes.c_uint64),
-                ("status", ctypes.c_void_p), ("status_host", ctypes.c_void_p)]
+NOISE_MAPS = ('eps_box', 'eps_attr', 'eps_depth', 'u_pres')
 
 
 # bit 0: disable the fused persistent per-cell kernels (tests compare both paths); bit 1: stage stamps; bit 2: no helper stream
@@ -132,8 +111,9 @@ class _StepFn(torch.autograd.Function):
     the parameter gradients are accumulated straight into the flat gradient buffer (the views
     behind every ``p.grad``) by ``spair_backward`` instead of being returned one tensor at a time.
     recon / z_where / z_pres are differentiable only with ``model.differentiable_outputs``; their
-    adjoints then enter the same reverse pass (``spair_backward_out``).  When ``x`` requires grad
-    the same pass also returns its gradient (``spair_backward_x``)."""
+    adjoints then enter the same reverse pass (``SpairStepIO.grad_recon`` / ``grad_z_where`` /
+    ``grad_z_pres``).  When ``x`` requires grad the same pass also returns its gradient
+    (``SpairStepIO.grad_x``)."""
 
     @staticmethod
     def forward(ctx, anchor, model, x, step, noise):
@@ -449,29 +429,35 @@ class SPAIR(nn.Module):
         e["generation"] += 1              # whatever this workspace held for an earlier forward is gone now
         self._last = dict(engine=e, st=st)
         inv_den = self._outgrad_buffers(e)[0] if train and self.differentiable_outputs else None
-        L.check(L.lib().spair_forward_out(ctypes.byref(d), ctypes.byref(st), L.ptr(self._flat), L.ptr(x), L.ptr(noise['eps_box']),
-                                          L.ptr(noise['eps_attr']), L.ptr(noise['eps_depth']), L.ptr(noise['u_pres']),
-                                          L.ptr(e['workspace']), L.ptr(loss_terms), L.ptr(recon), L.ptr(z_where), L.ptr(z_pres),
-                                          L.stream(), L.ptr(inv_den)), "spair_forward")
+        io = self._step_io(e, x, noise, loss_out=loss_terms, recon=recon, z_where=z_where, z_pres=z_pres, inv_den=inv_den)
+        L.check(L.lib().spair_forward(ctypes.byref(d), ctypes.byref(st), ctypes.byref(io), L.stream()), "spair_forward")
         return loss_terms, recon, z_where, z_pres
+
+    def _step_io(self, e, x, noise, **buffers):
+        """The SpairStepIO of a step on engine ``e``: the buffers both directions read, then ``buffers`` (field name -> tensor or None)."""
+        io = L.SpairStepIO(params=self._flat.data_ptr(), x=x.data_ptr(), workspace=e['workspace'].data_ptr())
+        for k in NOISE_MAPS:
+            setattr(io, k, noise[k].data_ptr())
+        for k, t in buffers.items():
+            if t is not None:             # (a field left alone is NULL)
+                setattr(io, k, t.data_ptr())
+        return io
 
     def _run_backward(self, x, step, noise, g_loss, e=None, g_recon=None, g_z_where=None, g_z_pres=None, grad_x=None, bce_target=True):
         """``g_recon`` / ``g_z_where`` / ``g_z_pres``: contiguous fp32 adjoints of the forward's outputs, or None (nothing launched for them).
-        ``grad_x``: a contiguous fp32 tensor shaped like ``x`` that receives the image gradient (overwritten), or None (spair_backward_out);
+        ``grad_x``: a contiguous fp32 tensor shaped like ``x`` that receives the image gradient (overwritten), or None (no image gradient);
         ``bce_target``: include the loss's BCE-target term in it."""
         e = e if e is not None else self._engine(x.shape[0])
         st = step_scalars(step, x.shape[0], self.world_size, True)
         self._bind_grads()
+        io = self._step_io(e, x, noise, grad_loss=g_loss, grads=self._flat_grad, inv_den=e.get('inv_den'), grad_recon=g_recon,
+                           grad_z_where=g_z_where, grad_z_pres=g_z_pres, aux_scratch=e.get('aux_scratch'), grad_x=grad_x,
+                           x_scratch=None if grad_x is None else self._input_grad_scratch(e))
+        io.bce_target = int(bool(bce_target))
         gb = self._grad_buckets
-        ev = gb.handles() if gb is not None else [ctypes.c_void_p(0)] * 3
-        args = (ctypes.byref(e['dims']), ctypes.byref(st), L.ptr(self._flat), L.ptr(x), L.ptr(noise['eps_box']), L.ptr(noise['eps_attr']),
-                L.ptr(noise['eps_depth']), L.ptr(noise['u_pres']), L.ptr(e['workspace']), L.ptr(g_loss), L.ptr(self._flat_grad), L.stream(),
-                ev[0], ev[1], ev[2], L.ptr(e.get('inv_den')), L.ptr(g_recon), L.ptr(g_z_where), L.ptr(g_z_pres), L.ptr(e.get('aux_scratch')))
-        if grad_x is None:
-            L.check(L.lib().spair_backward_out(*args), "spair_backward")
-        else:
-            L.check(L.lib().spair_backward_x(*args, L.ptr(grad_x), ctypes.c_int(int(bool(bce_target))), L.ptr(self._input_grad_scratch(e))),
-                    "spair_backward_x")
+        if gb is not None:
+            io.ev_decoder, io.ev_cells, io.ev_backbone = gb.handles()
+        L.check(L.lib().spair_backward(ctypes.byref(e['dims']), ctypes.byref(st), ctypes.byref(io), L.stream()), "spair_backward")
         if gb is not None:
             gb.pending = True             # ddp.allreduce_gradients(model) consumes the three events
 
@@ -495,7 +481,7 @@ class SPAIR(nn.Module):
         if noise is None:
             noise = self._draw_noise(e)
         else:
-            noise = {k: noise[k].to(x.device).contiguous().float() for k in ('eps_box', 'eps_attr', 'eps_depth', 'u_pres')}
+            noise = {k: noise[k].to(x.device).contiguous().float() for k in NOISE_MAPS}
             want = {k: tuple(v.shape) for k, v in e['noise'].items()}      # [B,{4,A,1,1},Gh,Gw]
             for k, v in noise.items():
                 if tuple(v.shape) != want[k]:

@@ -3,7 +3,8 @@
 * The oracle's autograd ``x.grad`` reproduces the reference's (tests/golden/xgrad_<case>.npz, make_golden_input_grad.py): after
   loss.backward(), inf pattern included (torch's BCE target gradient -logit(recon) is not clamped), and after a term on z_where / z_pres
   alone (the network path).  This pins the yardstick test_input_grad_gpu.py holds the engine to.
-* The built library exports spair_backward_x and the host-only scratch query, which returns [B,C,I,I] fp32 rounded to 256 bytes."""
+* The backward takes the image gradient's buffers in SpairStepIO (grad_x, x_scratch, bce_target); the built library exports it and the
+  host-only scratch query, which returns [B,C,I,I] fp32 rounded to 256 bytes."""
 import ctypes
 import os
 import re
@@ -80,11 +81,16 @@ def _lib():
     return _lib.lib()
 
 
-def test_input_gradient_entry_points_are_declared_and_exported():
+def test_input_gradient_io_fields_are_declared_and_exported():
     hdr = open(os.path.join(ROOT, "include", "spair_hip.h")).read()
-    for name in ("spair_backward_x", "spair_input_grad_scratch_bytes", "spair_input_grad_glimpse", "spair_input_grad_stem"):
+    for name in ("spair_backward", "spair_input_grad_scratch_bytes", "spair_input_grad_glimpse", "spair_input_grad_stem"):
         assert re.search(r"\b%s\s*\(" % name, hdr), name
         assert hasattr(_lib(), name), name
+    io = re.search(r"typedef struct SpairStepIO \{(.*?)\} SpairStepIO;", hdr, re.S).group(1)
+    for field in ("grad_x", "x_scratch", "bce_target"):
+        assert re.search(r"\b%s;" % field, io), field
+    gone = "spair_backward" + "_x"       # the suffixed entry point SpairStepIO replaced (spelled in parts: nothing else names it)
+    assert not re.search(r"\b%s\b" % gone, hdr) and not hasattr(_lib(), gone)
 
 
 @pytest.mark.parametrize("B,C,I,strides", [(256, 1, 128, (3, 2, 2, 1, 1, 1)), (3, 3, 48, (2, 2, 2, 1, 1, 1))])

@@ -1,4 +1,4 @@
-"""The gradient of the step with respect to its input image (``x.requires_grad_()``; spair_backward_x, csrc/input_grad.hip).
+"""The gradient of the step with respect to its input image (``x.requires_grad_()``; SpairStepIO.grad_x, csrc/input_grad.hip).
 
 * Kernel units against float64: the glimpse adjoint against the oracle's stn() autograd with respect to the image (border pile-up,
   tiny and 48-px boxes, align_corners 0 / 1, P 24 / 28 / 32, C 1 / 3), the stem's data gradient against conv2d's input gradient (k4 with

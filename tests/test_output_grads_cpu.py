@@ -1,5 +1,5 @@
-"""The differentiable-outputs switch of SPAIR on the host side (no GPU): constructor argument, attribute, default, and the two entry
-points of the C ABI it runs on (include/spair_hip.h).  The gradients themselves are checked in test_output_grads_gpu.py."""
+"""The differentiable-outputs switch of SPAIR on the host side (no GPU): constructor argument, attribute, default, and the entry points
+and SpairStepIO fields of the C ABI it runs on (include/spair_hip.h).  The gradients themselves are checked in test_output_grads_gpu.py."""
 import os
 import re
 
@@ -36,11 +36,17 @@ def test_switch_leaves_parameters_and_state_dict_alone():
     assert all(torch.equal(sa[k], sb[k]) for k in sa)
 
 
-def test_output_gradient_entry_points_are_declared_and_exported():
+def test_output_gradient_io_fields_are_declared_and_exported():
+    """spair_forward / spair_backward take the output gradients' buffers in SpairStepIO; the suffixed entry points that took them are gone."""
     from spair_pytorch_amd import _build, _lib
     hdr = open(os.path.join(ROOT, "include", "spair_hip.h")).read()
-    for name in ("spair_forward_out", "spair_backward_out"):
+    io = re.search(r"typedef struct SpairStepIO \{(.*?)\} SpairStepIO;", hdr, re.S).group(1)
+    for name in ("spair_forward", "spair_backward"):
         assert re.search(r"\b%s\s*\(" % name, hdr), name
+    for field in ("inv_den", "grad_recon", "grad_z_where", "grad_z_pres", "aux_scratch"):
+        assert re.search(r"\b%s;" % field, io), field
     _build.build(verbose=False)
     lib = _lib.lib()
-    assert hasattr(lib, "spair_forward_out") and hasattr(lib, "spair_backward_out")
+    assert hasattr(lib, "spair_forward") and hasattr(lib, "spair_backward")
+    for gone in ("spair_forward" + "_out", "spair_backward" + "_out", "spair_backward" + "_ev"):    # (spelled in parts: nothing else names them)
+        assert not re.search(r"\b%s\b" % gone, hdr) and not hasattr(lib, gone), gone

@@ -1,4 +1,4 @@
-"""Differentiable recon / z_where / z_pres outputs (SPAIR(..., differentiable_outputs=True); spair_forward_out / spair_backward_out,
+"""Differentiable recon / z_where / z_pres outputs (SPAIR(..., differentiable_outputs=True); SpairStepIO.inv_den and grad_*,
 csrc/outgrad.hip) against the oracle's autograd, which returns the three as live tensors of the same graph (models.py:35-131).
 
 A user term  aux = (Wr * recon).sum() + (Ww * z_where).sum() + (Wp * z_pres).sum()  with fixed non-symmetric random weights (a wrong

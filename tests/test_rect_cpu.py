@@ -1,5 +1,5 @@
 """Rectangular images ([C, H, W], H != W) on the host side: the per-axis geometry make_dims derives (the reference's own padding and grid,
-modules.py:68-105), the kernel plan a rectangular step gets (spair_step_plan_n: host arithmetic, no GPU), the geometry the C ABI refuses and
+modules.py:68-105), the kernel plan a rectangular step gets (spair_step_plan: host arithmetic, no GPU), the geometry the C ABI refuses and
 the ABI version check."""
 import ctypes
 
@@ -110,6 +110,7 @@ def test_workspace_of_a_rectangle_is_between_its_squares():
     assert 0 < small < rect < big
 
 
-def test_abi_version_matches():
+def test_abi_version_3_matches():
+    """Version 3: the step's entry points take SpairStepIO (include/spair_hip.h); the binding and the library agree on it."""
     from spair_pytorch_amd import _lib as L
-    assert L.lib().spair_abi_version() == L.ABI_VERSION == 2
+    assert L.lib().spair_abi_version() == L.ABI_VERSION == 3

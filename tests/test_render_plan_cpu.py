@@ -1,4 +1,4 @@
-"""The kernel plan of the training step (spair_step_plan / spair_step_plan_n: the host arithmetic make_ctx runs -- render_plan,
+"""The kernel plan of the training step (spair_step_plan: the host arithmetic make_ctx runs -- render_plan,
 chain_fwd_supported, dec_fused_supported, the backbone's and the decoder backward's predicates) for the configurations the suite covers.
 CPU only: the workspace is an address that is never dereferenced.
 
@@ -87,7 +87,7 @@ def test_step_plan_refuses_what_the_engine_refuses():
         L.step_plan(dims("bf16", 1, 28, 0, 48, 4), 0)
 
 
-# spair_step_plan_n: the default topology's layers 1 .. 6 are conv_1, conv_2 (4x4, stride 2 here) and four 1x1 layers (conv_3 .. conv_out),
+# spair_step_plan: the default topology's layers 1 .. 6 are conv_1, conv_2 (4x4, stride 2 here) and four 1x1 layers (conv_3 .. conv_out),
 # which run as the fused 1x1 stack in the bf16 step
 PW4 = ("PW_STACK",) * 4
 
@@ -155,14 +155,16 @@ def test_step_plan_n_conv_object_nets():
                                                                                          dec_wgrad_late=False)
 
 
-def test_step_plan_is_the_head_of_step_plan_n():
-    """spair_step_plan writes the first 8 ints of spair_step_plan_n; spair_step_plan_n writes min(n, SPAIR_STEP_PLAN_INTS) of them."""
+def test_step_plan_writes_the_first_n_ints():
+    """spair_step_plan writes min(n, SPAIR_STEP_PLAN_INTS) ints: step_plan reads the first 8 of them (out[7] = 0), step_plan_n all."""
     import ctypes
     from spair_pytorch_amd import _lib as L
     d = ctypes.byref(dims("bf16", 1, 28, 1, 64, 4))
-    full, head, part = (ctypes.c_int * L.STEP_PLAN_INTS)(), (ctypes.c_int * 8)(), (ctypes.c_int * L.STEP_PLAN_INTS)(*[-7] * L.STEP_PLAN_INTS)
-    L.check(L.lib().spair_step_plan_n(d, ctypes.c_void_p(WS), 16, 0, full, L.STEP_PLAN_INTS), "spair_step_plan_n")
-    L.check(L.lib().spair_step_plan(d, ctypes.c_void_p(WS), 16, head), "spair_step_plan")
-    L.check(L.lib().spair_step_plan_n(d, ctypes.c_void_p(WS), 16, 0, part, 10), "spair_step_plan_n")
+    n = L.STEP_PLAN_INTS
+    full, head, part = (ctypes.c_int * (n + 2))(*[-7] * (n + 2)), (ctypes.c_int * 8)(), (ctypes.c_int * n)(*[-7] * n)
+    L.check(L.lib().spair_step_plan(d, ctypes.c_void_p(WS), 16, 0, full, n + 2), "spair_step_plan")
+    L.check(L.lib().spair_step_plan(d, ctypes.c_void_p(WS), 16, 0, head, 8), "spair_step_plan")
+    L.check(L.lib().spair_step_plan(d, ctypes.c_void_p(WS), 16, 0, part, 10), "spair_step_plan")
+    assert list(full)[n:] == [-7, -7]
     assert list(head) == list(full)[:8] and full[7] == 0
-    assert list(part) == list(full)[:10] + [-7] * (L.STEP_PLAN_INTS - 10)
+    assert list(part) == list(full)[:10] + [-7] * (n - 10)

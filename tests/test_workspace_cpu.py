@@ -1,4 +1,4 @@
-"""The step workspace (spair_workspace_bytes) against the kernel plan (spair_step_plan / spair_step_plan_n).  The engine allocates an optional
+"""The step workspace (spair_workspace_bytes) against the kernel plan (spair_step_plan).  The engine allocates an optional
 buffer only where the plan of SpairStep.flags 0, no image gradient and an aligned base reads it; flags, an image gradient and a misaligned
 base may only turn kernels off.  CPU only: host arithmetic, the workspace is an address that is never dereferenced."""
 import ctypes

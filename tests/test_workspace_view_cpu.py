@@ -1,5 +1,5 @@
 """spair_workspace_view (host arithmetic): every named buffer of the step's workspace resolves, lies inside spair_workspace_bytes, overlaps no
-other one, and carries the element type the step plan (spair_step_plan / spair_step_plan_n) writes it in.  CPU only: the workspace is an
+other one, and carries the element type the step plan (spair_step_plan) writes it in.  CPU only: the workspace is an
 address that is never dereferenced.  The GPU side of the same view: tests/test_step_operands_gpu.py."""
 import pytest
 import torch

@@ -1,4 +1,4 @@
-"""Cost of the input-image gradient (x.requires_grad_(); spair_backward_x) on the benchmark step: ms per zero_grad + forward + backward + Adam
+"""Cost of the input-image gradient (x.requires_grad_(); SpairStepIO.grad_x) on the benchmark step: ms per zero_grad + forward + backward + Adam
 at BASELINE configs[1] (128x128, 16x16 grid, B=256, bf16) and configs[3] (256x256, 32x32 grid, B=64), without and with x.requires_grad.
 
     python tools/bench_input_grad.py                       # ms/step of the four runs
