@@ -425,6 +425,28 @@ int spair_render_fwd16m(const void* sprites_f16, int ld_s, const void* records, 
 int spair_render_bwd16r(const void* sprites_f16, int ld_s, const float* nbox, const float* pres, const float* depth, const void* records,
                         const float* aux, const float* grad_loss, void* dlogits_bf16, float* dnbox, float* dpres, float* ddepth,
                         int B, int HW, int C, int I, int P, int align_corners, float obj_scale, float alpha_scale, void* stream);
+/* ---- scene parse: the renderer's per-pixel assignment (csrc/render_owner.hip; the reference's composite, models.py:524-537, kept per
+ * object instead of summed).  For sample b, pixel (y, x) of the I x Iw canvas and cell k = h * Gw + w (ROW-MAJOR grid order), with the
+ * renderer's bilinear, zero-padded inverse-STN sampling:
+ *     a_k = warp(alpha_k * pres_k),  m_k = warp(max(alpha_k * pres_k * depth_k, 0.01)),  D = sum_k m_k + HW * 1e-9,
+ *     w_k = a_k (m_k + 1e-9) / D   (the coefficient of object k's colour in the composite),
+ *     coverage = sum_k w_k,  owner_weight = max_k w_k (always the raw maximum),
+ *     owner = the smallest k with w_k = owner_weight if that is > 0 and >= threshold, else -1,  area[b][k] = pixels of sample b with owner k.
+ * Outputs: owner int32 [B][I][Iw], owner_weight / coverage fp32 [B][I][Iw], area int32 [B][HW] (zeroed by the call; integer atomics).  No
+ * float atomics: bit-identical from run to run.  HW <= 1024.
+ * spair_render_owner (unit level): sprites [N][ld_s] of fp16 (s16 = 1) or fp32 elements, P*P texels of `ch` elements each with alpha (after
+ *   the sigmoid) LAST -- ch = 2: the grey (grey, alpha) pairs, ch = C + 1: the colour sprites; nbox [N][4], pres [N], depth [N]; cell k of
+ *   sample b is row r = (cidx ? cidx[k] : k) * B + b, cidx: HW device ints or NULL.
+ * spair_parse_owner (step level): the same on the sprites and the nbox / presence / depth rows the latest spair_forward left in
+ *   `workspace`, in the formats spair_step_plan(flags) says it wrote, through the workspace's own cell-to-row table. */
+int spair_render_owner(const void* sprites, int ld_s, int s16, int ch, const float* nbox, const float* pres, const float* depth,
+                       const int* cidx, float threshold, int* owner, float* owner_weight, float* coverage, int* area, int B, int HW, int I,
+                       int Iw, int P, int align_corners, void* stream);
+int spair_parse_owner(const SpairDims* d, const void* workspace, int flags, float threshold, int* owner, float* owner_weight,
+                      float* coverage, int* area, void* stream);
+/* The cell-to-row table of a workspace (written by the first spair_forward on it): out[k] = cprime of cell k = h * Gw + w, G * Gw device
+ * ints; the per-cell rows of spair_workspace_view are r = cprime * B + b. */
+int spair_cell_rows(const SpairDims* d, const void* workspace, int* out, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -78,8 +78,19 @@ def lib():
                         (h.spair_step_plan, [ctypes.POINTER(SpairDims), ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                              ctypes.POINTER(ctypes.c_int), ctypes.c_int])):
             f.argtypes, f.restype = args, ctypes.c_int
+        _declare_parse(h)
         _lib = h
     return _lib
+
+
+def _declare_parse(h):
+    """Argument lists of the scene-parse entry points (include/spair_hip.h, "scene parse"): they take a float by value."""
+    vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    h.spair_render_owner.argtypes = [vp, i, i, i, vp, vp, vp, vp, f, vp, vp, vp, vp, i, i, i, i, i, i, vp]
+    h.spair_parse_owner.argtypes = [ctypes.POINTER(SpairDims), vp, i, f, vp, vp, vp, vp, vp]
+    h.spair_cell_rows.argtypes = [ctypes.POINTER(SpairDims), vp, vp, vp]
+    for fn in (h.spair_render_owner, h.spair_parse_owner, h.spair_cell_rows):
+        fn.restype = i
 
 
 def check(rc, what):
@@ -148,3 +159,25 @@ def workspace_view(dims, workspace, name, flags=0, input_grad=False):
     check(lib().spair_workspace_view(ctypes.byref(dims), ctypes.c_void_p(int(workspace)), int(flags), int(bool(input_grad)),
                                      name.encode(), out), "spair_workspace_view(%s)" % name)
     return dict(offset=out[0], rows=out[1], cols=out[2], ld=out[3], dtype=VIEW_DTYPES[out[4]], written=bool(out[5]))
+
+
+def render_owner(sprites, channels, nbox, pres, depth, B, HW, I, Iw, P, align_corners=False, threshold=0.5, cell_rows=None):
+    """spair_render_owner on torch tensors: ``sprites`` [B*HW, >= P*P*channels] fp16 or fp32 (its row stride is the leading dimension),
+    ``channels`` elements per texel with alpha last, ``nbox`` [B*HW, 4], ``pres`` / ``depth`` [B*HW]; cell k of sample b is row
+    ``(cell_rows[k] if cell_rows is not None else k) * B + b``.  Returns (owner int32 [B,I,Iw], owner_weight, coverage fp32 [B,I,Iw],
+    area int32 [B,HW])."""
+    if sprites.dtype not in (torch.float16, torch.float32) or sprites.stride(1) != 1:
+        raise SpairHipError("sprites must be fp16 or fp32 rows")
+    dev = sprites.device
+    owner = torch.empty(B, I, Iw, device=dev, dtype=torch.int32)
+    weight, cover = (torch.empty(B, I, Iw, device=dev, dtype=torch.float32) for _ in range(2))
+    area = torch.empty(B, HW, device=dev, dtype=torch.int32)
+    nbox, pres, depth = (t.contiguous().float() for t in (nbox, pres, depth))
+    rows = None if cell_rows is None else cell_rows.to(device=dev, dtype=torch.int32).contiguous()
+    if sprites.shape[0] != B * HW or nbox.numel() != 4 * B * HW or pres.numel() != B * HW or depth.numel() != B * HW or \
+            (rows is not None and rows.numel() != HW):
+        raise SpairHipError("render_owner: operands do not have B * HW rows")
+    check(lib().spair_render_owner(ptr(sprites), int(sprites.stride(0)), int(sprites.dtype == torch.float16), int(channels), ptr(nbox),
+                                   ptr(pres), ptr(depth), ptr(rows), float(threshold), ptr(owner), ptr(weight), ptr(cover), ptr(area),
+                                   int(B), int(HW), int(I), int(Iw), int(P), int(bool(align_corners)), stream()), "spair_render_owner")
+    return owner, weight, cover, area

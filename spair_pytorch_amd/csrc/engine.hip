@@ -1805,3 +1805,29 @@ extern "C" int spair_export_map(const SpairDims* d0, const void* workspace, int 
     else return SPAIR_ERR_SHAPE;
     return misc_export(src, ld, col0, ch, w.cell_h, w.cell_w, d->B, d->G, d->Gw, out, s);
 }
+
+// ---- scene parse (render_owner.hip) ---------------------------------------------------------------------------------
+// The per-pixel owner map of the latest spair_forward on this workspace: its sprites (in the format the step plan of `flags` wrote them)
+// and its rows' nbox / presence / depth, walked in row-major cell order through the workspace's cell-to-row table.
+extern "C" int spair_parse_owner(const SpairDims* d0, const void* workspace, int flags, float threshold, int* owner, float* owner_weight,
+                                 float* coverage, int* area, void* stream) {
+    if (!d0 || !workspace || !owner || !owner_weight || !coverage || !area) return SPAIR_ERR_SHAPE;
+    const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
+    TRY(validate(*d));
+    const CellLayout L = make_cell_layout(*d);
+    const Ws w = carve(*d, const_cast<void*>(workspace));
+    const StepPlan p = plan_step(*d, flags, false, workspace);
+    return render_owner(render_geom(*d, L, &w.cb), w.S, w.ld_s, p.rp.s16, d->C + 1, w.cidx, threshold, owner, owner_weight, coverage, area,
+                        (hipStream_t)stream);
+}
+
+// The workspace's cell-to-row table: out[k] (device, HW = G * Gw ints) = cprime of cell k = h * Gw + w, whose rows are r = cprime * B + b.
+// Written by the first spair_forward on the workspace.
+extern "C" int spair_cell_rows(const SpairDims* d0, const void* workspace, int* out, void* stream) {
+    if (!d0 || !workspace || !out) return SPAIR_ERR_SHAPE;
+    const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
+    TRY(validate(*d));
+    const Ws w = carve(*d, const_cast<void*>(workspace));
+    return hipMemcpyAsync(out, w.cidx, sizeof(int) * (size_t)d->G * d->Gw, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess
+               ? SPAIR_OK : SPAIR_ERR_LAUNCH;
+}

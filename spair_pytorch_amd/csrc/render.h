@@ -51,3 +51,8 @@ struct RenderPlan {
 // 16-bit sprites and d-logits: the bf16 step's grey images with the MLP object decoder (the conv decoder and the colour kernels take fp32)
 inline bool render_16bit(const SpairDims& d) { return d.dtype == SPAIR_BF16 && d.C == 1 && !d.obj_conv; }
 RenderPlan render_plan(const SpairDims& d, const RenderGeom& g, int ld_s, const float* S, const void* rec, const float* dlogits);
+
+// render_owner.hip: the scene parse's per-pixel owner map (arg-max of the composite's per-object coefficients; its own kernel family for
+// every sprite format: s16 fp16 / fp32 elements, CH elements per texel with alpha last).  cidx: cell k (row-major) -> row block, or null
+int render_owner(const RenderGeom& g, const float* S, int ld_s, int s16, int CH, const int* cidx, float threshold, int* owner,
+                 float* owner_weight, float* coverage, int* area, hipStream_t s);

@@ -96,6 +96,38 @@ def step_scalars(global_step, batch, world_size=1, train=True):
     return st
 
 
+def parse_boxes(z_where, image_h, image_w, align_corners=False):
+    """Pixel boxes of the cells of ``z_where`` [B,4,G,Gw] = (xt, yt, xs, ys): [B, G*Gw, 4] = (x0, y0, x1, y1), cell order k = h * Gw + w.
+    The box is the footprint of the sprite's P x P texel square as the renderer places it (centre convention: a pixel centre is at
+    index + 0.5): x0 = (xt - xs/2) * Iw, x1 = (xt + xs/2) * Iw, y likewise with yt, ys and I.  With ``align_corners`` the same normalised
+    extent g through (g + 1) / 2 * (n - 1) + 0.5.  (``metric.py`` keeps the reference's top-left reading of z_where; this does not.)"""
+    B = z_where.shape[0]
+    xt, yt, xs, ys = (z_where[:, i].reshape(B, -1) for i in range(4))
+    lo_hi = torch.stack((xt - 0.5 * xs, yt - 0.5 * ys, xt + 0.5 * xs, yt + 0.5 * ys), dim=-1)
+    if align_corners:
+        n = lo_hi.new_tensor([image_w - 1, image_h - 1, image_w - 1, image_h - 1])
+        return lo_hi * n + 0.5
+    return lo_hi * lo_hi.new_tensor([image_w, image_h, image_w, image_h])
+
+
+class ParseResult:
+    """What ``SPAIR.parse`` returns: the scene as objects and as a per-pixel owner map (device tensors; cell order k = h * Gw + w).
+
+    ``loss_terms`` [9], ``recon`` [B,C,I,Iw], ``z_where`` [B,4,G,Gw], ``z_pres`` / ``z_depth`` [B,1,G,Gw], ``z_what`` [B,A,G,Gw];
+    ``boxes`` [B,G*Gw,4] (x0, y0, x1, y1) in pixels (``parse_boxes``);
+    ``owner`` int32 [B,I,Iw]: the cell whose weight in the renderer's composite is largest at the pixel (lowest k on a tie), -1 where that
+    weight is 0 or below the threshold; ``owner_weight`` [B,I,Iw]: that largest weight, whatever the threshold; ``coverage`` [B,I,Iw]:
+    the sum of all cells' weights (in [0, 1]); ``area`` int32 [B,G*Gw]: pixels owned per cell."""
+    __slots__ = ("loss_terms", "recon", "z_where", "z_pres", "z_depth", "z_what", "boxes", "owner", "owner_weight", "coverage", "area")
+
+    def __init__(self, **fields):
+        for k in self.__slots__:
+            setattr(self, k, fields[k])
+
+    def __repr__(self):
+        return "ParseResult(%s)" % ", ".join("%s=%s" % (k, tuple(getattr(self, k).shape)) for k in self.__slots__)
+
+
 class _NullWriter:
     def __getattr__(self, name):
         return lambda *a, **k: None
@@ -496,6 +528,64 @@ class SPAIR(nn.Module):
         self._log_scalars()
         self.dist_param, self.dist = _LazyDist(self), _LazyDist(self, as_normal=True)
         return loss, recon, z_where, z_pres
+
+    def _mean_noise(self, e):
+        """The posterior mean as noise maps of engine ``e`` (constant, allocated on first use): zero eps_*, u_pres = 0.5, whose logistic
+        noise log(u + eps) - log(1 - u + eps) is exactly 0.  Nothing is drawn."""
+        if e.get("mean_noise") is None:
+            e["mean_noise"] = {k: torch.full_like(v, 0.5 if k == "u_pres" else 0.0) for k, v in e["noise"].items()}
+        return e["mean_noise"]
+
+    def parse(self, x, global_step=0, sample=False, threshold=0.5, noise=None):
+        """Read the scene out of the model: one ``no_grad`` forward and the renderer's per-pixel assignment, as a ``ParseResult``.
+
+        ``sample=False`` (default) takes the posterior mean (zero eps_*, u_pres = 0.5) from constant maps: the answer is repeatable and
+        NOTHING is drawn from torch's generators, so parse calls between training steps leave the training run's noise sequence alone.
+        ``sample=True`` draws as ``forward`` does; ``noise`` is the dict ``forward`` takes and wins over both.  ``global_step`` only moves
+        the count-prior term of ``loss_terms``.  ``threshold``: a pixel whose largest composite weight is below it (or 0) gets owner -1;
+        ``owner_weight`` is the raw maximum either way.
+
+        Like any forward it overwrites the workspace of that batch size: ``backward()`` of an earlier forward of the same batch size
+        raises afterwards (the generation check).  And as any ``no_grad`` forward, it rewrites the step-status word ``FusedAdam`` reads as
+        its skip flag: do not call it between ``backward()`` and ``FusedAdam.step()``."""
+        self._ensure_ready()
+        if not x.is_cuda:
+            raise L.SpairHipError("input must be on the MI355X (got %s); there is no CPU path" % x.device)
+        x = x.contiguous().float()
+        if list(x.shape[1:]) != list(self.image_shape):
+            raise AssertionError("expected input [B,%s], got %s" % (self.image_shape, tuple(x.shape)))
+        if self.raise_on_nonfinite and self._status_host[0] != 0:
+            raise L.SpairHipError(self._status_text(self._status_host[0]) + " -- seen by a later parse(); clear_step_status() to go on")
+        e = self._engine(x.shape[0])
+        if noise is not None:
+            noise = {k: noise[k].to(x.device).contiguous().float() for k in NOISE_MAPS}
+            for k, v in noise.items():
+                if tuple(v.shape) != tuple(e['noise'][k].shape):
+                    raise AssertionError("noise[%r]: expected %s, got %s" % (k, tuple(e['noise'][k].shape), tuple(v.shape)))
+        else:
+            noise = self._draw_noise(e) if sample else self._mean_noise(e)
+        with torch.no_grad():
+            terms, recon, z_where, z_pres = self._run_forward(x, int(global_step), noise, train=False)
+            self._loss_terms = terms
+            d = e['dims']
+            (B, I), (Iw, Gw) = (d.B, d.I), dims_width(d)
+            owner = torch.empty(B, I, Iw, device=x.device, dtype=torch.int32)
+            weight, coverage = (torch.empty(B, I, Iw, device=x.device, dtype=torch.float32) for _ in range(2))
+            area = torch.empty(B, d.G * Gw, device=x.device, dtype=torch.int32)
+            L.check(L.lib().spair_parse_owner(ctypes.byref(d), L.ptr(e['workspace']), int(STEP_FLAGS), float(threshold), L.ptr(owner),
+                                              L.ptr(weight), L.ptr(coverage), L.ptr(area), L.stream()), "spair_parse_owner")
+            return ParseResult(loss_terms=terms[:9], recon=recon, z_where=z_where, z_pres=z_pres, z_depth=self.export_map(1),
+                               z_what=self.export_map(0), boxes=parse_boxes(z_where, I, Iw, bool(d.align_corners)), owner=owner,
+                               owner_weight=weight, coverage=coverage, area=area)
+
+    def cell_rows(self, batch=None):
+        """The cell-to-row table of the workspace of batch size ``batch`` (default: the latest forward's), int32 [G*Gw]: the per-cell rows
+        of ``workspace_view`` for cell k = h * Gw + w are ``cell_rows()[k] * B + b`` (spair_cell_rows)."""
+        e = self._last_engine() if batch is None else self._engine(batch)
+        d = e['dims']
+        out = torch.empty(d.G * dims_width(d)[1], device=self.device, dtype=torch.int32)
+        L.check(L.lib().spair_cell_rows(ctypes.byref(d), L.ptr(e['workspace']), L.ptr(out), L.stream()), "spair_cell_rows")
+        return out
 
     def _log_scalars(self):
         w = self.writer
