@@ -447,6 +447,27 @@ int spair_parse_owner(const SpairDims* d, const void* workspace, int flags, floa
 /* The cell-to-row table of a workspace (written by the first spair_forward on it): out[k] = cprime of cell k = h * Gw + w, G * Gw device
  * ints; the per-cell rows of spair_workspace_view are r = cprime * B + b. */
 int spair_cell_rows(const SpairDims* d, const void* workspace, int* out, void* stream);
+/* ---- scene composition: a scene rendered from GIVEN latents (csrc/compose.hip; the reference's _render, models.py:452-542, is a pure
+ * function of them), and its composite kept per requested object.
+ * spair_compose: z_where [B][4][G][Gw] = (xt, yt, xs, ys), z_what [B][A][G][Gw], z_depth / z_pres [B][1][G][Gw] (device, fp32, taken as
+ *   given: nothing is clamped) -> recon [B][C][I][Iw] and, where inv_den is not NULL, the composite's 1/D per pixel [B][I][Iw].  It runs the
+ *   cell tables, the object decoder's share of the weight preparation from `params`, the latents into the workspace's per-cell rows (the
+ *   inverse of spair_export_map 0 / 1; nbox = z_where), then the decoder and the renderer forward that spair_step_plan(flags) names -- what
+ *   spair_forward runs after its per-cell chain.  No backbone, no chain, no KL, no loss: SpairStep.status is not written.  It overwrites
+ *   the workspace's decoder / renderer buffers as any forward does (a spair_backward of an earlier forward on it is then meaningless).
+ * spair_render_layers: on the sprites and rows the latest spair_compose / spair_forward left in `workspace`, for cells [B][K] (device
+ *   ints, row-major cell index k = h * Gw + w; any value outside [0, G * Gw): an all-zero layer; duplicates allowed) and that call's inv_den:
+ *     layer_weight[b][j] = a_k (m_k + 1e-9) / D  (the w_k of the scene parse above),  layers[b][j][c] = layer_weight[b][j] * warp(colour_k[c]),
+ *   layers [B][K][C][I][Iw], layer_weight [B][K][I][Iw], every element written (zeros outside a footprint).  The sum of the layers of ALL
+ *   cells is recon before its clamp.  No atomics: bit-identical from run to run.
+ * spair_render_layers_rows (unit level): the same on explicit operands, laid out as for spair_render_owner; ch = 2 .. 4. */
+int spair_compose(const SpairDims* d, const float* params, void* workspace, int flags, const float* z_where, const float* z_what,
+                  const float* z_depth, const float* z_pres, float* recon, float* inv_den, void* stream);
+int spair_render_layers(const SpairDims* d, const void* workspace, int flags, const int* cells, int K, const float* inv_den, float* layers,
+                        float* layer_weight, void* stream);
+int spair_render_layers_rows(const void* sprites, int ld_s, int s16, int ch, const float* nbox, const float* pres, const float* depth,
+                             const int* cidx, const int* cells, int K, const float* inv_den, float* layers, float* layer_weight, int B,
+                             int HW, int I, int Iw, int P, int align_corners, void* stream);
 #ifdef __cplusplus
 }
 #endif

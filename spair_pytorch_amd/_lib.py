@@ -79,6 +79,7 @@ def lib():
                                              ctypes.POINTER(ctypes.c_int), ctypes.c_int])):
             f.argtypes, f.restype = args, ctypes.c_int
         _declare_parse(h)
+        _declare_compose(h)
         _lib = h
     return _lib
 
@@ -90,6 +91,16 @@ def _declare_parse(h):
     h.spair_parse_owner.argtypes = [ctypes.POINTER(SpairDims), vp, i, f, vp, vp, vp, vp, vp]
     h.spair_cell_rows.argtypes = [ctypes.POINTER(SpairDims), vp, vp, vp]
     for fn in (h.spair_render_owner, h.spair_parse_owner, h.spair_cell_rows):
+        fn.restype = i
+
+
+def _declare_compose(h):
+    """Argument lists of the scene-composition entry points (include/spair_hip.h, "scene composition")."""
+    vp, i = ctypes.c_void_p, ctypes.c_int
+    h.spair_compose.argtypes = [ctypes.POINTER(SpairDims), vp, vp, i, vp, vp, vp, vp, vp, vp, vp]
+    h.spair_render_layers.argtypes = [ctypes.POINTER(SpairDims), vp, i, vp, i, vp, vp, vp, vp]
+    h.spair_render_layers_rows.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, i, vp, vp, vp, i, i, i, i, i, i, vp]
+    for fn in (h.spair_compose, h.spair_render_layers, h.spair_render_layers_rows):
         fn.restype = i
 
 
@@ -181,3 +192,25 @@ def render_owner(sprites, channels, nbox, pres, depth, B, HW, I, Iw, P, align_co
                                    ptr(pres), ptr(depth), ptr(rows), float(threshold), ptr(owner), ptr(weight), ptr(cover), ptr(area),
                                    int(B), int(HW), int(I), int(Iw), int(P), int(bool(align_corners)), stream()), "spair_render_owner")
     return owner, weight, cover, area
+
+
+def render_layers(sprites, channels, nbox, pres, depth, cells, inv_den, B, HW, I, Iw, P, align_corners=False, cell_rows=None):
+    """spair_render_layers_rows on torch tensors: operands as for ``render_owner``; ``cells`` int [B,K] (row-major cell index, anything
+    outside [0, HW) = an all-zero layer), ``inv_den`` fp32 [B,I,Iw] (the composite's 1/D per pixel).  Returns (layers fp32
+    [B,K,channels-1,I,Iw], layer_weight fp32 [B,K,I,Iw])."""
+    if sprites.dtype not in (torch.float16, torch.float32) or sprites.stride(1) != 1:
+        raise SpairHipError("sprites must be fp16 or fp32 rows")
+    dev = sprites.device
+    cells = cells.to(device=dev, dtype=torch.int32).contiguous()
+    K = int(cells.shape[1])
+    nbox, pres, depth, inv_den = (t.contiguous().float() for t in (nbox, pres, depth, inv_den))
+    rows = None if cell_rows is None else cell_rows.to(device=dev, dtype=torch.int32).contiguous()
+    if sprites.shape[0] != B * HW or nbox.numel() != 4 * B * HW or pres.numel() != B * HW or depth.numel() != B * HW or \
+            cells.shape[0] != B or inv_den.numel() != B * I * Iw or (rows is not None and rows.numel() != HW):
+        raise SpairHipError("render_layers: operands do not have B * HW rows / B * I * Iw pixels")
+    layers = torch.empty(B, K, int(channels) - 1, I, Iw, device=dev, dtype=torch.float32)
+    weight = torch.empty(B, K, I, Iw, device=dev, dtype=torch.float32)
+    check(lib().spair_render_layers_rows(ptr(sprites), int(sprites.stride(0)), int(sprites.dtype == torch.float16), int(channels), ptr(nbox),
+                                         ptr(pres), ptr(depth), ptr(rows), ptr(cells), K, ptr(inv_den), ptr(layers), ptr(weight), int(B),
+                                         int(HW), int(I), int(Iw), int(P), int(bool(align_corners)), stream()), "spair_render_layers_rows")
+    return layers, weight

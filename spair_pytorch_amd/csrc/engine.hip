@@ -17,6 +17,7 @@
 #include "dec_fused.h"
 #include "objconv.h"
 #include "render.h"
+#include "compose.h"
 
 #define TRY(expr)                      \
     do {                               \
@@ -642,7 +643,8 @@ static const void* bptr(const void* base, size_t elem_off, int dtype) {
 }
 
 // ---- weight preparation ----------------------------------------------------------------------------
-// part 0: the backbone's conv weights (what conv_1 waits for); part 1: everything else (first needed by the per-cell chain)
+// part 0: the backbone's conv weights (what conv_1 waits for); part 1: everything else (first needed by the per-cell chain); part 2: the
+// object decoder's share of part 1 alone (spair_compose)
 static int prep_weights(Ctx& c, bool need_dgrad, int part) {
     std::vector<PrepEntry> es;
     const int bf = c.d.dtype == SPAIR_BF16;
@@ -672,7 +674,7 @@ static int prep_weights(Ctx& c, bool need_dgrad, int part) {
             }
         }
     }
-    for (int id = 0; part == 1 && id < LIN_COUNT; ++id) {
+    for (int id = part == 2 ? LIN_DEC0 : 0; part >= 1 && id < LIN_COUNT; ++id) {
         if (id == LIN_BOXH0 || id == LIN_ZH0) continue;
         const LinSpec& l = c.PL.lin[id];
         if (!l.in || !l.out) continue;        // (the convolutional variant has no dense0 / dense1 in its encoder, no dense1 / out in its decoder)
@@ -709,7 +711,7 @@ static int prep_weights(Ctx& c, bool need_dgrad, int part) {
         for (int cw = 0; need_dgrad && cw < CW_COUNT; ++cw)
             if (CHAIN_PACK[cw].ntt) pack(c.w.chain_wt, cw, 5, 1);
     }
-    if (part == 1 && c.use_dec_fused)
+    if (part >= 1 && c.use_dec_fused)
         TRY(dec_fused_pack(c.params + c.PL.lin[LIN_DEC0].w, c.params + c.PL.lin[LIN_DEC1].w, c.params + c.PL.lin[LIN_DEC2].w, c.d.A,
                            c.d.P * c.d.P * (c.d.C + 1), c.d.obj_logit_scale, c.d.alpha_logit_scale, c.w.dec_stream, c.s));
     if (part == 1) {
@@ -762,16 +764,16 @@ static GemmNT dgrad_classes16(const Ctx& c, int i) {
 }
 
 // what both directions share: the buffers they both read (checked here, once), the normalised dims, their layouts and the step plan
-static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const SpairStepIO* io, void* stream, bool input_grad = false) {
-    if (!d || !st || !io || !io->params || !io->x || !io->eps_box || !io->eps_attr || !io->eps_depth || !io->u_pres || !io->workspace)
-        return SPAIR_ERR_SHAPE;
+// (ctx_init: without the step's image and noise maps -- what spair_compose, which runs no backbone and no per-cell chain, works on)
+static int ctx_init(Ctx& c, const SpairDims* d, const SpairStep* st, const float* params, void* workspace, void* stream, bool input_grad) {
+    if (!d || !st || !params || !workspace) return SPAIR_ERR_SHAPE;
     c.d = spair_dims_norm(*d); c.st = *st;
     TRY(validate(c.d));
     d = &c.d;
     c.L = make_cell_layout(*d);
     c.PL = make_param_layout(*d);
-    c.w = carve(*d, io->workspace);
-    c.params = io->params; c.x = io->x; c.s = (hipStream_t)stream; c.tn_part = c.w.tn_part;
+    c.w = carve(*d, workspace);
+    c.params = params; c.x = nullptr; c.s = (hipStream_t)stream; c.tn_part = c.w.tn_part;
     CellHyper& H = c.H;
     H.wheel = st->wheel; H.kl_scale = st->kl_scale * d->vae_beta; H.img = (float)d->I; H.anchor = d->anchor;
     H.cell_over_img = (float)((double)d->cell_px / (double)d->I);
@@ -782,10 +784,17 @@ static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const Spair
     for (int i = 0; i < 6; ++i) { H.prior_mean[i] = d->prior_mean[i]; H.prior_std[i] = d->prior_std[i]; }
     H.count_prior_prob = st->count_prior_prob;
     c.w.cb.edge = c.params + c.PL.edge;
-    c.w.cb.eps_box = io->eps_box; c.w.cb.eps_attr = io->eps_attr; c.w.cb.eps_depth = io->eps_depth; c.w.cb.u_pres = io->u_pres;
     fill_diag(c);
-    static_cast<StepPlan&>(c) = plan_step(*d, st->flags, input_grad, io->workspace);
+    static_cast<StepPlan&>(c) = plan_step(*d, st->flags, input_grad, workspace);
     c.rg = render_geom(*d, c.L, &c.w.cb);
+    return SPAIR_OK;
+}
+static int make_ctx(Ctx& c, const SpairDims* d, const SpairStep* st, const SpairStepIO* io, void* stream, bool input_grad = false) {
+    if (!d || !st || !io || !io->params || !io->x || !io->eps_box || !io->eps_attr || !io->eps_depth || !io->u_pres || !io->workspace)
+        return SPAIR_ERR_SHAPE;
+    TRY(ctx_init(c, d, st, io->params, io->workspace, stream, input_grad));
+    c.x = io->x;
+    c.w.cb.eps_box = io->eps_box; c.w.cb.eps_attr = io->eps_attr; c.w.cb.eps_depth = io->eps_depth; c.w.cb.u_pres = io->u_pres;
     return SPAIR_OK;
 }
 
@@ -1141,6 +1150,53 @@ static int cells_fwd(Ctx& c) {
     return SPAIR_OK;
 }
 
+// The object decoder of the plan (models.py:474-492): the decoder's input rows Za (fp32) / Za16 (bf16 step) -> the sprites S.  Shared by
+// spair_forward and spair_compose.
+static int decoder_fwd(Ctx& c) {
+    const SpairDims* d = &c.d;
+    const CellLayout& L = c.L;
+    const ParamLayout& PL = c.PL;
+    const int N = L.N;
+    const int per = d->P * d->P * (d->C + 1);
+    const int b16 = d->dtype == SPAIR_BF16;
+    const int K0 = round_up(PL.lin[LIN_DEC0].in, 8), K2 = round_up(PL.lin[LIN_DEC2].in, 8);
+    if (PL.oc_n) return oc_decoder_fwd(c);
+    if (c.use_dec_fused) {
+        // all three layers + the sprite epilogue in one activation-stationary launch (dec_fused.hip)
+        ProfScope p2(PS_DEC2_FWD, c.s);
+        return dec_fused_fwd(c.w.Za16, L.ld_rec, c.w.dec_stream, c.params + PL.lin[LIN_DEC0].b, c.params + PL.lin[LIN_DEC1].b, c.params + PL.lin[LIN_DEC2].b,
+                             c.w.Hd1, c.w.Hd2, c.w.S, c.w.ld_s, N, d->A, per, d->obj_logit_scale, d->alpha_logit_scale, d->alpha_logit_bias, c.s);
+    }
+    if (b16) {   // hidden activations stored as bf16
+        TRY(nt16(c, c.w.Za16, L.ld_rec, c.w.lin_wf[LIN_DEC0], K0, c.w.Hd1, SP_DEC_H1, 1, N, SP_DEC_H1, K0, c.params + PL.lin[LIN_DEC0].b, nullptr, 0, 1));
+        TRY(nt16(c, c.w.Hd1, SP_DEC_H1, c.w.lin_wf[LIN_DEC1], SP_DEC_H1, c.w.Hd2, SP_DEC_H2, 1, N, SP_DEC_H2, SP_DEC_H1,
+                 c.params + PL.lin[LIN_DEC1].b, nullptr, 0, 1));
+    } else {
+        TRY(fwd_lin(c, LIN_DEC0, c.w.Za, L.ld_rec, c.w.Hd1, SP_DEC_H1, 0, N, c.params + PL.lin[LIN_DEC0].b, SP_DEC_H1, 1));
+        TRY(fwd_lin(c, LIN_DEC1, c.w.Hd1, SP_DEC_H1, c.w.Hd2, SP_DEC_H2, 0, N, c.params + PL.lin[LIN_DEC1].b, SP_DEC_H2, 1));
+    }
+    // decoder.out with the sprite sigmoid epilogue fused (models.py:485-492)
+    ProfScope p2(PS_DEC2_FWD, c.s);
+    GemmNT g;
+    memset(&g, 0, sizeof(g));
+    g.A = c.w.Hd2; g.lda = SP_DEC_H2; g.B = c.w.lin_wf[LIN_DEC2]; g.ldb = K2; g.C = c.w.S; g.ldc = c.w.ld_s; g.M = N; g.N = per; g.K = K2;
+    g.bias = c.params + PL.lin[LIN_DEC2].b; g.sprite_ch = d->C + 1;
+    g.c_bf16 = c.rp.s16;      // bf16 step: the sprites leave as 16-bit (grey, alpha) pairs -- half the bytes for the renderer, both
+                              // ways (colour images: fp32 sprites for the generic-channel renderer)
+    g.obj_scale = d->obj_logit_scale; g.alpha_scale = d->alpha_logit_scale; g.alpha_bias = d->alpha_logit_bias;
+    if (b16) return spair_gemm_nt16_impl(g, false, c.s);
+    return spair_gemm_nt_impl(g, false, d->dtype, c.s);
+}
+
+// The renderer forward of the plan on the workspace's sprites and rows; x: the BCE target, aux: null outside a training forward.  Shared by
+// spair_forward and spair_compose.
+static int render_fwd(Ctx& c, const float* x, float* recon, float* aux, float* inv_den) {
+    if (c.rp.fwd == RENDER_MMA) return render_fwd_mma(c.rg, c.w.S, c.w.ld_s, c.w.rrec, x, recon, aux, c.w.bce_partial, inv_den, c.s);
+    if (c.rp.fwd == RENDER_GEN2) return render_fwd2(c.rg, c.w.S, c.w.ld_s, c.rp.s16, x, recon, aux, c.w.bce_partial, inv_den, c.s);
+    if (c.rp.fwd == RENDER_GEN1) return render_fwd1(c.rg, c.w.S, c.w.ld_s, c.rp.s16, x, recon, aux, c.w.bce_partial, inv_den, c.s);
+    return render_fwd_c(c.rg, c.w.S, c.w.ld_s, c.d.C, x, recon, aux, c.w.bce_partial, inv_den, c.s);
+}
+
 extern "C" int spair_forward(const SpairDims* d, const SpairStep* st, const SpairStepIO* io, void* stream) {
     Ctx c;
     TRY(make_ctx(c, d, st, io, stream));
@@ -1192,53 +1248,15 @@ extern "C" int spair_forward(const SpairDims* d, const SpairStep* st, const Spai
         if (gauss_on_main) TRY(loss_gauss_kl(L, P, c.H, c.w.kl_partial, c.s));
     }
     if (c.rp.rec) TRY(render_prep(c.rg, c.w.rrec, c.s));
-    // decoder (models.py:474-492)
-    const ParamLayout& PL = c.PL;
-    const int N = L.N;
-    const int per = d->P * d->P * (d->C + 1);
     {
         ProfScope ps(PS_DECODER_FWD, c.s);
-        const int b16 = d->dtype == SPAIR_BF16;
-        const int K0 = round_up(PL.lin[LIN_DEC0].in, 8), K2 = round_up(PL.lin[LIN_DEC2].in, 8);
-        if (b16 && !c.use_chain) TRY(spair_to_bf16(c.w.Za, L.ld_rec, c.w.Za16, L.ld_rec, N, L.ld_rec, c.s));     // the fused chain writes bf16 itself
-        if (PL.oc_n) {
-            TRY(oc_decoder_fwd(c));
-        } else if (c.use_dec_fused) {
-            // all three layers + the sprite epilogue in one activation-stationary launch (dec_fused.hip)
-            ProfScope p2(PS_DEC2_FWD, c.s);
-            TRY(dec_fused_fwd(c.w.Za16, L.ld_rec, c.w.dec_stream, c.params + PL.lin[LIN_DEC0].b, c.params + PL.lin[LIN_DEC1].b, c.params + PL.lin[LIN_DEC2].b,
-                              c.w.Hd1, c.w.Hd2, c.w.S, c.w.ld_s, N, d->A, per, d->obj_logit_scale, d->alpha_logit_scale, d->alpha_logit_bias, c.s));
-        } else {
-        if (b16) {   // hidden activations stored as bf16
-            TRY(nt16(c, c.w.Za16, L.ld_rec, c.w.lin_wf[LIN_DEC0], K0, c.w.Hd1, SP_DEC_H1, 1, N, SP_DEC_H1, K0, c.params + PL.lin[LIN_DEC0].b, nullptr, 0, 1));
-            TRY(nt16(c, c.w.Hd1, SP_DEC_H1, c.w.lin_wf[LIN_DEC1], SP_DEC_H1, c.w.Hd2, SP_DEC_H2, 1, N, SP_DEC_H2, SP_DEC_H1,
-                     c.params + PL.lin[LIN_DEC1].b, nullptr, 0, 1));
-        } else {
-            TRY(fwd_lin(c, LIN_DEC0, c.w.Za, L.ld_rec, c.w.Hd1, SP_DEC_H1, 0, N, c.params + PL.lin[LIN_DEC0].b, SP_DEC_H1, 1));
-            TRY(fwd_lin(c, LIN_DEC1, c.w.Hd1, SP_DEC_H1, c.w.Hd2, SP_DEC_H2, 0, N, c.params + PL.lin[LIN_DEC1].b, SP_DEC_H2, 1));
-        }
-        {   // decoder.out with the sprite sigmoid epilogue fused (models.py:485-492)
-            ProfScope p2(PS_DEC2_FWD, c.s);
-            GemmNT g;
-            memset(&g, 0, sizeof(g));
-            g.A = c.w.Hd2; g.lda = SP_DEC_H2; g.B = c.w.lin_wf[LIN_DEC2]; g.ldb = K2; g.C = c.w.S; g.ldc = c.w.ld_s; g.M = N; g.N = per; g.K = K2;
-            g.bias = c.params + PL.lin[LIN_DEC2].b; g.sprite_ch = d->C + 1;
-            g.c_bf16 = c.rp.s16;      // bf16 step: the sprites leave as 16-bit (grey, alpha) pairs -- half the bytes for the renderer, both
-                                      // ways (colour images: fp32 sprites for the generic-channel renderer)
-            g.obj_scale = d->obj_logit_scale; g.alpha_scale = d->alpha_logit_scale; g.alpha_bias = d->alpha_logit_bias;
-            if (b16) TRY(spair_gemm_nt16_impl(g, false, c.s));
-            else TRY(spair_gemm_nt_impl(g, false, d->dtype, c.s));
-        }
-        }
+        if (d->dtype == SPAIR_BF16 && !c.use_chain) TRY(spair_to_bf16(c.w.Za, L.ld_rec, c.w.Za16, L.ld_rec, L.N, L.ld_rec, c.s));     // the fused chain writes bf16 itself
+        TRY(decoder_fwd(c));
     }
     // KL + render + loss
     {
         ProfScope ps(PS_RENDER_FWD, c.s);
-        float* const aux = st->train ? c.w.aux : nullptr;
-        if (c.rp.fwd == RENDER_MMA) TRY(render_fwd_mma(c.rg, c.w.S, c.w.ld_s, c.w.rrec, c.x, io->recon, aux, c.w.bce_partial, io->inv_den, c.s));
-        else if (c.rp.fwd == RENDER_GEN2) TRY(render_fwd2(c.rg, c.w.S, c.w.ld_s, c.rp.s16, c.x, io->recon, aux, c.w.bce_partial, io->inv_den, c.s));
-        else if (c.rp.fwd == RENDER_GEN1) TRY(render_fwd1(c.rg, c.w.S, c.w.ld_s, c.rp.s16, c.x, io->recon, aux, c.w.bce_partial, io->inv_den, c.s));
-        else TRY(render_fwd_c(c.rg, c.w.S, c.w.ld_s, d->C, c.x, io->recon, aux, c.w.bce_partial, io->inv_den, c.s));
+        TRY(render_fwd(c, c.x, io->recon, st->train ? c.w.aux : nullptr, io->inv_den));
     }
     if (side && hipStreamWaitEvent(c.s, side->ev[1], 0) != hipSuccess) return SPAIR_ERR_LAUNCH;
     ProfScope psl(PS_LOSS, c.s);
@@ -1830,4 +1848,43 @@ extern "C" int spair_cell_rows(const SpairDims* d0, const void* workspace, int* 
     const Ws w = carve(*d, const_cast<void*>(workspace));
     return hipMemcpyAsync(out, w.cidx, sizeof(int) * (size_t)d->G * d->Gw, hipMemcpyDeviceToDevice, (hipStream_t)stream) == hipSuccess
                ? SPAIR_OK : SPAIR_ERR_LAUNCH;
+}
+
+// ---- scene composition from given latents (compose.hip) ---------------------------------------------------------------
+// The step from its latents on: the cell tables, the decoder's share of the weight preparation (the parameters may have changed since the
+// last step), the latents into the workspace's rows (k_latents_import), then what spair_forward runs after its per-cell chain with the
+// same plan (plan_step / render_plan of `flags`): the renderer's records, the object decoder, the renderer forward.  No backbone, no
+// chain, no KL, no loss: the step-status word is not touched.  The renderer forwards want a BCE target and a partials buffer: the
+// workspace's aux plane (whatever it holds) and bce_partial serve, their result is never read.  Everything on the caller's stream.
+extern "C" int spair_compose(const SpairDims* d0, const float* params, void* workspace, int flags, const float* z_where, const float* z_what,
+                             const float* z_depth, const float* z_pres, float* recon, float* inv_den, void* stream) {
+    if (!z_where || !z_what || !z_depth || !z_pres || !recon) return SPAIR_ERR_SHAPE;
+    SpairStep st;
+    memset(&st, 0, sizeof(st));
+    st.flags = flags;
+    Ctx c;
+    TRY(ctx_init(c, d0, &st, params, workspace, stream, false));
+    const SpairDims& d = c.d;
+    TRY(cells_init_tables(d.G, d.Gw, c.L.LB, c.w.cell_h, c.w.cell_w, c.w.cidx, c.w.nbr, c.w.cons, c.w.diag_start, c.s));
+    TRY(prep_weights(c, false, 2));
+    TRY(latents_import(c.L, c.w.cell_h, c.w.cell_w, z_where, z_what, z_depth, z_pres, c.w.cb.nbox, c.w.cb.rec, c.w.Za,
+                       d.dtype == SPAIR_BF16 ? c.w.Za16 : nullptr, c.s));
+    if (c.rp.rec) TRY(render_prep(c.rg, c.w.rrec, c.s));
+    TRY(decoder_fwd(c));
+    return render_fwd(c, c.w.aux, recon, nullptr, inv_den);
+}
+
+// The object layers of the scene the latest spair_compose or spair_forward left in `workspace` (its sprites in the format the step plan of
+// `flags` wrote them, its rows' nbox / presence / depth): cells [B][K] device ints (row-major cell index; outside [0, G * Gw): an all-zero
+// layer), inv_den [B][I][Iw] as that call stored it; layers [B][K][C][I][Iw], layer_weight [B][K][I][Iw].
+extern "C" int spair_render_layers(const SpairDims* d0, const void* workspace, int flags, const int* cells, int K, const float* inv_den,
+                                   float* layers, float* layer_weight, void* stream) {
+    if (!d0 || !workspace || !cells || !inv_den || !layers || !layer_weight) return SPAIR_ERR_SHAPE;
+    const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
+    TRY(validate(*d));
+    const CellLayout L = make_cell_layout(*d);
+    const Ws w = carve(*d, const_cast<void*>(workspace));
+    const StepPlan p = plan_step(*d, flags, false, workspace);
+    return render_layers(render_geom(*d, L, &w.cb), w.S, w.ld_s, p.rp.s16, d->C + 1, w.cidx, cells, K, inv_den, layers, layer_weight,
+                         (hipStream_t)stream);
 }

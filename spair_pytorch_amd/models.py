@@ -128,6 +128,22 @@ class ParseResult:
         return "ParseResult(%s)" % ", ".join("%s=%s" % (k, tuple(getattr(self, k).shape)) for k in self.__slots__)
 
 
+class ComposeResult:
+    """What ``SPAIR.compose`` returns (device tensors): ``recon`` [B,C,I,Iw], ``boxes`` [B,G*Gw,4] (``parse_boxes`` of the given z_where)
+    and, when ``layers`` was given, ``layers`` [B,K,C,I,Iw] and ``layer_weight`` [B,K,I,Iw] (else None): per requested cell k its
+    coefficient in the composite, ``a_k (m_k + 1e-9) / D``, and that coefficient times its warped colour.  The layers of all cells sum
+    to ``recon`` (before its clamp to [0, 1], which never acts)."""
+    __slots__ = ("recon", "boxes", "layers", "layer_weight")
+
+    def __init__(self, **fields):
+        for k in self.__slots__:
+            setattr(self, k, fields[k])
+
+    def __repr__(self):
+        return "ComposeResult(%s)" % ", ".join("%s=%s" % (k, None if getattr(self, k) is None else tuple(getattr(self, k).shape))
+                                               for k in self.__slots__)
+
+
 class _NullWriter:
     def __getattr__(self, name):
         return lambda *a, **k: None
@@ -577,6 +593,74 @@ class SPAIR(nn.Module):
             return ParseResult(loss_terms=terms[:9], recon=recon, z_where=z_where, z_pres=z_pres, z_depth=self.export_map(1),
                                z_what=self.export_map(0), boxes=parse_boxes(z_where, I, Iw, bool(d.align_corners)), owner=owner,
                                owner_weight=weight, coverage=coverage, area=area)
+
+    def compose(self, scene=None, *, z_where=None, z_what=None, z_depth=None, z_pres=None, layers=None):
+        """Render a scene from GIVEN latents: the decoder and the renderer of the step, nothing inferred (the reference's ``_render``,
+        models.py:452-542, a pure function of the four latents).  Returns a ``ComposeResult``.
+
+        ``scene``: any object with ``z_where`` [B,4,G,Gw] = (xt, yt, xs, ys), ``z_what`` [B,A,G,Gw], ``z_depth`` and ``z_pres``
+        [B,1,G,Gw] -- a ``ParseResult`` qualifies; a keyword tensor replaces that field.  Device tensors (converted with
+        ``.float().contiguous()``).  The values are taken AS GIVEN: ``z_pres`` and ``z_depth`` are not clamped to [0, 1], box sizes are not
+        checked (a zero or negative size gives an empty object).
+
+        ``layers``: optional int tensor [B,K] of cell indices k = h * Gw + w.  The result then also holds, per requested cell,
+        ``layer_weight`` = a_k (m_k + 1e-9) / D and ``layers`` = layer_weight * warp(colour_k), with a_k = warp(alpha_k pres_k),
+        m_k = warp(max(alpha_k pres_k depth_k, 0.01)) and D the sum of m over ALL cells (+ G Gw 1e-9).  Any value outside [0, G*Gw) means
+        "skip" and gives an all-zero layer (nothing is validated on the host: no synchronisation); duplicates are allowed.
+
+        Removing an object means ``z_pres = 0`` for its cell.  That is not the same as dropping the object from the sum: its importance
+        floor 0.01 stays in D inside its footprint, exactly as in the reference, so the objects it overlapped stay slightly dimmed there.
+
+        ``no_grad`` and deterministic: nothing is drawn (no torch generator is touched), no loss is computed, and the step-status word
+        ``FusedAdam`` reads is NOT written, so -- unlike ``parse`` -- it is safe between ``backward()`` and ``FusedAdam.step()``.  Like any
+        forward it overwrites the workspace of that batch size: ``backward()`` of an earlier forward of the same batch size raises
+        afterwards (the generation check), and ``export_map`` / ``workspace_view`` then show the composed scene."""
+        self._ensure_ready()
+        given = dict(z_where=z_where, z_what=z_what, z_depth=z_depth, z_pres=z_pres)
+        lat = {}
+        for k, v in given.items():
+            if v is None:
+                v = getattr(scene, k, None)
+            if v is None:
+                raise AssertionError("compose: no %s (neither in `scene` nor as a keyword)" % k)
+            if not torch.is_tensor(v) or not v.is_cuda:
+                raise L.SpairHipError("compose: %s must be a tensor on the MI355X; there is no CPU path" % k)
+            lat[k] = v.detach().float().contiguous()
+        B = int(lat["z_where"].shape[0]) if lat["z_where"].dim() == 4 else 0
+        if B < 1:
+            raise AssertionError("compose: z_where must be [B,4,G,Gw], got %s" % (tuple(lat["z_where"].shape),))
+        e = self._engine(B)
+        d = e['dims']
+        (I, G), (Iw, Gw) = (d.I, d.G), dims_width(d)
+        for k, ch in (("z_where", 4), ("z_what", d.A), ("z_depth", 1), ("z_pres", 1)):
+            if tuple(lat[k].shape) != (B, ch, G, Gw):
+                raise AssertionError("compose: %s: expected %s, got %s" % (k, (B, ch, G, Gw), tuple(lat[k].shape)))
+        cells = None
+        if layers is not None:
+            if not torch.is_tensor(layers) or not layers.is_cuda:
+                raise L.SpairHipError("compose: layers must be an int tensor on the MI355X")
+            if layers.dim() != 2 or layers.shape[0] != B or layers.shape[1] < 1 or layers.is_floating_point():
+                raise AssertionError("compose: layers: expected an int tensor [%d,K], got %s %s" % (B, layers.dtype, tuple(layers.shape)))
+            # (an index beyond int32 is outside the grid either way: it stays outside)
+            cells = layers.clamp(-1, G * Gw).to(torch.int32).contiguous()
+        dev = lat["z_where"].device
+        with torch.no_grad():
+            recon = torch.empty(B, d.C, I, Iw, device=dev, dtype=torch.float32)
+            inv_den = torch.empty(B, I, Iw, device=dev, dtype=torch.float32) if cells is not None else None
+            e["generation"] += 1              # whatever this workspace held for an earlier forward is gone now
+            self._last = dict(engine=e, st=None)
+            L.check(L.lib().spair_compose(ctypes.byref(d), L.ptr(self._flat), L.ptr(e['workspace']), int(STEP_FLAGS), L.ptr(lat["z_where"]),
+                                          L.ptr(lat["z_what"]), L.ptr(lat["z_depth"]), L.ptr(lat["z_pres"]), L.ptr(recon), L.ptr(inv_den),
+                                          L.stream()), "spair_compose")
+            out_layers = weight = None
+            if cells is not None:
+                K = int(cells.shape[1])
+                out_layers = torch.empty(B, K, d.C, I, Iw, device=dev, dtype=torch.float32)
+                weight = torch.empty(B, K, I, Iw, device=dev, dtype=torch.float32)
+                L.check(L.lib().spair_render_layers(ctypes.byref(d), L.ptr(e['workspace']), int(STEP_FLAGS), L.ptr(cells), K, L.ptr(inv_den),
+                                                    L.ptr(out_layers), L.ptr(weight), L.stream()), "spair_render_layers")
+            return ComposeResult(recon=recon, boxes=parse_boxes(lat["z_where"], I, Iw, bool(d.align_corners)), layers=out_layers,
+                                 layer_weight=weight)
 
     def cell_rows(self, batch=None):
         """The cell-to-row table of the workspace of batch size ``batch`` (default: the latest forward's), int32 [G*Gw]: the per-cell rows
