@@ -89,7 +89,11 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     }
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
-__device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }  // (0,1)
+// [2^-25, 1], not (0,1): the smallest draw is 0.5 * 2^-24; from 2^23 on the + 0.5f is a tie that rounds to even, so the largest,
+// (float)(2^24 - 1) + 0.5f, rounds to 2^24 and the top draw returns exactly 1.0f.  pres_forward takes u == 1 through its +1e-9; the
+// Box-Muller radius is then 0 (tests/test_latent_edges_gpu.py runs a step on both extremes).
+// The mapping is left as it is: every seeded run depends on it.
+__device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 __global__ __launch_bounds__(256) void k_noise(uint64_t seed, float* eps_box, long long n_box, float* eps_attr, long long n_attr,
                                                float* eps_depth, long long n_depth, float* u_pres, long long n_pres) {
