@@ -473,10 +473,14 @@ static std::vector<PInfo> param_infos(const SpairDims& d) {
     return v;
 }
 
-extern "C" int spair_param_count(const SpairDims* d) { return d ? (int)param_infos(spair_dims_norm(*d)).size() : -1; }
-extern "C" int64_t spair_param_total(const SpairDims* d) { return d ? make_param_layout(spair_dims_norm(*d)).total : -1; }
+// the layer counts index fixed arrays of the layouts: a caller's struct with more layers than they hold is refused before any layout is made
+static bool layer_counts_ok(const SpairDims* d) {
+    return d && d->n_conv >= 1 && d->n_conv <= SP_MAX_CONV && (!d->obj_conv || (d->oc_n >= 1 && d->oc_n <= 4));
+}
+extern "C" int spair_param_count(const SpairDims* d) { return layer_counts_ok(d) ? (int)param_infos(spair_dims_norm(*d)).size() : -1; }
+extern "C" int64_t spair_param_total(const SpairDims* d) { return layer_counts_ok(d) ? make_param_layout(spair_dims_norm(*d)).total : -1; }
 extern "C" int spair_param_info(const SpairDims* d, int idx, char* name, int name_cap, int64_t* offset, int64_t* shape4, int* ndim) {
-    if (!d) return SPAIR_ERR_SHAPE;
+    if (!layer_counts_ok(d)) return SPAIR_ERR_SHAPE;
     const std::vector<PInfo> v = param_infos(spair_dims_norm(*d));
     if (idx < 0 || idx >= (int)v.size()) return SPAIR_ERR_SHAPE;
     snprintf(name, name_cap, "%s", v[idx].name);

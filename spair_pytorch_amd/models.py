@@ -56,8 +56,10 @@ def make_dims(batch, image_shape, topology, dtype=None, object_conv_topology=Non
     if Iw != I:      # (square: the three width fields stay 0 = "the same as I, G, pad_post", the C ABI's square meaning)
         d.Iw, d.Gw, d.pad_post_w = Iw, int(Gw), int(post_w)
     d.P, d.A, d.F, d.NP = int(cfg.OBJECT_SHAPE[0]), int(cfg.N_ATTRIBUTES), int(cfg.N_BACKBONE_FEATURES), int(cfg.N_PASSTHROUGH_FEATURES)
+    # (a topology longer than the struct's per-layer arrays keeps its count: the library refuses it -- spair_workspace_bytes <= 0 -- as it
+    # refuses any other configuration it does not run)
     d.n_conv = len(topology)
-    for i, layer in enumerate(topology):
+    for i, layer in enumerate(topology[:len(d.conv_k)]):
         d.conv_k[i], d.conv_s[i] = int(layer['kernel_size']), int(layer['stride'])
         d.conv_c[i] = int(layer.get('filters', layer.get('out_channels')))
     d.pad_pre, d.pad_post, d.cell_px = pre, post, cell
@@ -274,7 +276,9 @@ class SPAIR(nn.Module):
             self.object_decoder = ObjectConvDecoder(cfg.N_ATTRIBUTES, chan + 1, self.object_encoder.shapes, self.object_conv_topology)
         else:
             self.object_decoder = build_MLP(cfg.N_ATTRIBUTES, obj_dim * obj_dim * (chan + 1), hidden_layers=[128, 256])
-        self.attn = _SelfAttnParams(55)   # dead in the reference (models.py:120,167); kept for state_dict parity
+        # dead in the reference (models.py:120,167); kept for state_dict parity.  One context record without its presence: the 55 channels
+        # the reference writes out for N_ATTRIBUTES = 50, as the library's parameter layout sizes it for any N_ATTRIBUTES
+        self.attn = _SelfAttnParams(4 + cfg.N_ATTRIBUTES + 1)
 
     def _build_edge_element(self):
         sizes = [4, cfg.N_ATTRIBUTES, 1, 1]
@@ -298,6 +302,8 @@ class SPAIR(nn.Module):
         lib.spair_param_total.restype = ctypes.c_int64
         total = lib.spair_param_total(ctypes.byref(d))
         n = lib.spair_param_count(ctypes.byref(d))
+        if total <= 0 or n <= 0:
+            raise L.SpairHipError("unsupported configuration for the HIP engine (image=%s, topology=%s)" % (self.image_shape, self.backbone.topology))
         named = dict(self.named_parameters())
         dev = self.device
         flat = torch.zeros(total, dtype=torch.float32, device=dev)

@@ -18,20 +18,26 @@ OBJ_PX = 28
 CONTEXT_DIM = 4 * (4 + N_ATTR + 1 + 1)  # 224 (N_LOOKBACK = 1)
 
 
-def context_dim(lookback=1):
+def context_dim(lookback=1, n_attr=N_ATTR):
     """models.py:26: ((2L+1)^2 // 2) records of 4 + A + 2."""
-    return (2 * lookback + 1) ** 2 // 2 * (4 + N_ATTR + 1 + 1)
+    return (2 * lookback + 1) ** 2 // 2 * (4 + n_attr + 1 + 1)
 
 
-def param_shapes(in_chan=1, conv_kernels=(4, 4, 4, 1, 1, 1), filters=128, lookback=1, obj_px=OBJ_PX):
-    """Ordered {key: shape} for every tensor of the reference state_dict."""
+def param_shapes(in_chan=1, conv_kernels=(4, 4, 4, 1, 1, 1), filters=128, lookback=1, obj_px=OBJ_PX, n_features=N_BACKBONE_FEATURES,
+                 n_passthrough=N_PASSTHROUGH, n_attr=N_ATTR):
+    """Ordered {key: shape} for every tensor of the reference state_dict.  ``filters``: one count for every backbone layer, or one per
+    layer (config.py:7-14 DEFAULT_BACKBONE_TOPOLOGY); ``n_features`` / ``n_passthrough`` / ``n_attr``: config.py:22,24,27."""
+    N_BACKBONE_FEATURES, N_PASSTHROUGH, N_ATTR = n_features, n_passthrough, n_attr
+    if isinstance(filters, int):
+        filters = (filters,) * len(conv_kernels)
+    assert len(filters) == len(conv_kernels)
     s = {}
     s["virtual_edge_element"] = (4 + N_ATTR + 2,)
     prev = in_chan
-    for i, k in enumerate(conv_kernels):
-        s[f"backbone.net.conv_{i}.weight"] = (filters, prev, k, k)
-        s[f"backbone.net.conv_{i}.bias"] = (filters,)
-        prev = filters
+    for i, (f, k) in enumerate(zip(filters, conv_kernels)):
+        s[f"backbone.net.conv_{i}.weight"] = (f, prev, k, k)
+        s[f"backbone.net.conv_{i}.bias"] = (f,)
+        prev = f
     s["backbone.net.conv_out.weight"] = (N_BACKBONE_FEATURES, prev, 1, 1)
     s["backbone.net.conv_out.bias"] = (N_BACKBONE_FEATURES,)
 
@@ -50,7 +56,7 @@ def param_shapes(in_chan=1, conv_kernels=(4, 4, 4, 1, 1, 1), filters=128, lookba
             s[f"{prefix}.out.weight"] = (outs, p)
             s[f"{prefix}.out.bias"] = (outs,)
 
-    CONTEXT_DIM = context_dim(lookback)
+    CONTEXT_DIM = context_dim(lookback, N_ATTR)
     box_in = N_BACKBONE_FEATURES + CONTEXT_DIM
     mlp("box_network", box_in, (100, 100), (8, N_PASSTHROUGH), True)
     mlp("object_encoder", obj_px * obj_px * in_chan, (256, 128), 2 * N_ATTR, False)
@@ -58,19 +64,23 @@ def param_shapes(in_chan=1, conv_kernels=(4, 4, 4, 1, 1, 1), filters=128, lookba
     mlp("z_network", z_in, (100, 100), (2, N_PASSTHROUGH), True)
     mlp("obj_network", z_in + 1, (100, 100), 1, False)
     mlp("object_decoder", N_ATTR, (128, 256), obj_px * obj_px * (in_chan + 1), False)
+    # the dead Self_Attn over one context record without its presence: 4 + A + 1 channels (models.py:167 writes the 55 of A = 50 out; the
+    # reference cannot be built with another A, the engine's parameter layout follows the formula)
+    ad = 4 + N_ATTR + 1
     s["attn.gamma"] = (1,)
-    for nm, o in (("query", 55 // 8), ("key", 55 // 8), ("value", 55)):
-        s[f"attn.{nm}_conv.weight"] = (o, 55, 1, 1)
+    for nm, o in (("query", ad // 8), ("key", ad // 8), ("value", ad)):
+        s[f"attn.{nm}_conv.weight"] = (o, ad, 1, 1)
         s[f"attn.{nm}_conv.bias"] = (o,)
     return s
 
 
-def make_weights(seed, scale=1.0, in_chan=1, lookback=1, obj_px=OBJ_PX):
+def make_weights(seed, scale=1.0, in_chan=1, lookback=1, obj_px=OBJ_PX, **net):
     """U(-1/sqrt(fan_in), 1/sqrt(fan_in)) * scale per tensor (PyTorch-default-like
-    magnitude), float32.  Returns {key: np.ndarray}."""
+    magnitude), float32.  Returns {key: np.ndarray}.  ``net``: param_shapes' conv_kernels / filters / n_features / n_passthrough / n_attr
+    (default: the reference's network, whose streams every earlier fixture was drawn from)."""
     rng = np.random.default_rng(seed)
     out = {}
-    shapes = param_shapes(in_chan, lookback=lookback, obj_px=obj_px)
+    shapes = param_shapes(in_chan, lookback=lookback, obj_px=obj_px, **net)
     for key, shp in shapes.items():
         if key == "virtual_edge_element":
             t = rng.standard_normal(shp).astype(np.float32)
@@ -91,9 +101,10 @@ def make_weights(seed, scale=1.0, in_chan=1, lookback=1, obj_px=OBJ_PX):
     return out
 
 
-def make_noise(seed, B, G):
+def make_noise(seed, B, G, n_attr=N_ATTR):
     """The 7 per-cell draws of the reference (models.py:333-336,84,95,402-403), laid out
     as maps.  eps_box channel order = draw order (cy, cx, height, width)."""
+    N_ATTR = n_attr
     rng = np.random.default_rng(seed)
     return dict(
         eps_box=rng.standard_normal((B, 4, G, G)).astype(np.float32),
@@ -166,15 +177,75 @@ OBJ_CASES = {
 }
 
 
+# other backbone topologies and network sizes (config.py:7-14 DEFAULT_BACKBONE_TOPOLOGY, :22 N_BACKBONE_FEATURES, :24 N_PASSTHROUGH_FEATURES):
+# `topology` = (filters, kernel, stride) per layer, F / NP / A = features / passthrough / attributes; what is absent is the default network
+# (tests/test_topology_cpu.py pins the kernels each one runs, tests/test_topology_gpu.py runs them)
+_S2 = (2, 2, 2, 1, 1, 1)
+TOPO_CASES = {
+    "t_shallow64": dict(I=32, topology=((64, 4, 2), (64, 4, 2), (64, 1, 1)), B=4, step=1001, wseed=31, wscale=1.0, max_objects=3),
+    "t_k3": dict(I=48, topology=((128, 3, 2), (128, 3, 1), (128, 2, 2), (128, 1, 1), (128, 1, 1)), B=2, step=1001, wseed=32, wscale=1.0,
+                 max_objects=3),
+    "t_k6": dict(I=48, topology=((128, 4, 2), (128, 6, 2), (128, 4, 2), (128, 1, 1)), B=4, step=1001, wseed=33, wscale=1.0, max_objects=3),
+    "t_nostack": dict(I=48, topology=((128, 4, 2), (128, 4, 2), (128, 4, 2)), B=4, step=1001, wseed=34, wscale=1.0, max_objects=3),
+    "t_deep8": dict(I=48, topology=((32, 4, 2), (64, 4, 2), (128, 4, 2), (128, 1, 1), (72, 1, 1), (128, 1, 1), (128, 1, 1), (128, 1, 1)),
+                    B=2, step=1001, wseed=35, wscale=1.0, max_objects=3),
+    # (wseed 36 put one decoder hidden unit's pre-activation 9e-9 from its ReLU kink, inside fp32 summation-order noise: which side it falls on,
+    # and with it that unit's gradient, is then decided by the order of a sum, not by the model -- the other cases' smallest is 6e-7 .. 8e-5)
+    "t_stack5": dict(I=32, topology=((128, 4, 2), (128, 4, 2)) + ((128, 1, 1),) * 4, B=4, step=1001, wseed=45, wscale=1.0, max_objects=3),
+    "t_stem5": dict(I=48, topology=((128, 5, 4), (128, 2, 2), (128, 1, 1)), B=4, step=1001, wseed=37, wscale=1.0, max_objects=3),
+    "t_feat64": dict(I=48, strides=_S2, F=64, NP=36, B=4, step=1001, wseed=38, wscale=1.0, max_objects=3),
+    "t_feat128": dict(I=48, strides=_S2, F=128, NP=64, B=4, step=1001, wseed=39, wscale=1.0, max_objects=3),
+}
+# N_ATTRIBUTES other than 50 (config.py:27): the reference cannot run them (models.py:66,167 write 55 context channels out), so there is no
+# fixture -- the oracle, pinned to the reference on every other case, stands in for it (tests/test_topology_gpu.py)
+ORACLE_CASES = {
+    "o_attr16": dict(I=48, strides=_S2, A=16, B=4, step=1001, wseed=40, wscale=1.0, max_objects=3),
+    "o_attr59": dict(I=48, strides=_S2, A=59, B=2, step=1001, wseed=41, wscale=1.0, max_objects=3),
+}
+
+
 def all_cases():
     d = dict(CASES)
     d.update(LOOKBACK_CASES)
     d.update(RGB_CASES)
     d.update(OBJ_CASES)
+    d.update(TOPO_CASES)
     return d
 
 
-def grid_side(I, strides, kernels=(4, 4, 4, 1, 1, 1)):
+def case_topology(case):
+    """(filters, kernel, stride) per backbone layer of a case: its `topology`, or the default network with the case's strides."""
+    if "topology" in case:
+        return tuple(tuple(int(v) for v in layer) for layer in case["topology"])
+    return tuple((128, k, int(s)) for k, s in zip((4, 4, 4, 1, 1, 1), case["strides"]))
+
+
+def case_net(case):
+    """The keyword arguments of param_shapes / make_weights that a case's topology and sizes stand for."""
+    topo = case_topology(case)
+    return dict(conv_kernels=tuple(k for _, k, _ in topo), filters=tuple(f for f, _, _ in topo), n_features=case.get("F", N_BACKBONE_FEATURES),
+                n_passthrough=case.get("NP", N_PASSTHROUGH), n_attr=case.get("A", N_ATTR))
+
+
+def case_strides(case):
+    return tuple(s for _, _, s in case_topology(case))
+
+
+def case_grid(case):
+    return grid_side(case["I"], case_strides(case))
+
+
+def case_inputs(case):
+    """(weights, image, noise) of a case, as make_golden.py feeds them to the reference."""
+    w = make_weights(case["wseed"], case["wscale"], in_chan=case.get("in_chan", 1), lookback=case.get("lookback", 1),
+                     obj_px=case.get("obj_px", OBJ_PX), **case_net(case))
+    x = make_image(100 + case["wseed"], case["B"], case["I"], case["max_objects"], in_chan=case.get("in_chan", 1))
+    noise = make_noise(200 + case["wseed"], case["B"], case_grid(case), n_attr=case.get("A", N_ATTR))
+    return w, x, noise
+
+
+def grid_side(I, strides, kernels=None):
+    """Cells per side: ceil(I / product of the strides) (modules.py:68-105; the kernels only move the padding)."""
     cell = 1
     for s in strides:
         cell *= s

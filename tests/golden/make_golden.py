@@ -32,7 +32,9 @@ REF = "/root/reference"
 SMALL = 4096  # tensors up to this many elements get their full gradient stored
 
 
-def _import_reference(I, strides, B, G, lookback=1, in_chan=1, obj_px=gi.OBJ_PX):
+def _import_reference(I, strides, B, G, lookback=1, in_chan=1, obj_px=gi.OBJ_PX, topology=None, n_features=None, n_passthrough=None):
+    """``topology``: (filters, kernel, stride) per backbone layer, replacing the default list (then ``strides`` is not read);
+    ``n_features`` / ``n_passthrough``: N_BACKBONE_FEATURES / N_PASSTHROUGH_FEATURES.  All are set before ``spair.models`` is imported."""
     import matplotlib
     matplotlib.use("Agg")
     tb = types.ModuleType("tensorboardX")
@@ -53,8 +55,15 @@ def _import_reference(I, strides, B, G, lookback=1, in_chan=1, obj_px=gi.OBJ_PX)
     cfg.BATCH_SIZE = B
     cfg.N_LOOKBACK = lookback
     cfg.OBJECT_SHAPE[:] = [obj_px, obj_px]
-    for layer, s in zip(cfg.DEFAULT_BACKBONE_TOPOLOGY, strides):
-        layer["stride"] = s
+    if topology is not None:
+        cfg.DEFAULT_BACKBONE_TOPOLOGY[:] = [dict(filters=f, kernel_size=k, stride=s) for f, k, s in topology]
+    else:
+        for layer, s in zip(cfg.DEFAULT_BACKBONE_TOPOLOGY, strides):
+            layer["stride"] = s
+    if n_features is not None:
+        cfg.N_BACKBONE_FEATURES = int(n_features)
+    if n_passthrough is not None:
+        cfg.N_PASSTHROUGH_FEATURES = int(n_passthrough)
     from spair import models, modules, debug_tools
     debug_tools.GRID_SIZE = G
     return cfg, models, modules, SummaryWriter
@@ -64,15 +73,19 @@ def run_case(name):
     import torch
     case = gi.all_cases()[name]
     in_chan = case.get("in_chan", 1)
-    I, strides, B, step = case["I"], case["strides"], case["B"], case["step"]
+    I, strides, B, step = case["I"], gi.case_strides(case), case["B"], case["step"]
     G = gi.grid_side(I, strides)
     obj_px = case.get("obj_px", gi.OBJ_PX)
-    cfg, models, modules, SummaryWriter = _import_reference(I, strides, B, G, case.get("lookback", 1), in_chan, obj_px)
+    net = gi.case_net(case)
+    if net["n_attr"] != gi.N_ATTR:
+        raise SystemExit("the reference cannot run N_ATTRIBUTES != 50 (models.py:66,167): no fixture for " + name)
+    cfg, models, modules, SummaryWriter = _import_reference(I, strides, B, G, case.get("lookback", 1), in_chan, obj_px, gi.case_topology(case),
+                                                            net["n_features"], net["n_passthrough"])
     torch.manual_seed(3)
     with contextlib.redirect_stdout(io.StringIO()):
         m = models.SPAIR(cfg.INPUT_IMAGE_SHAPE, SummaryWriter(), torch.device("cpu"))
-    assert tuple(m.feature_space_dim) == (100, G, G), m.feature_space_dim
-    w = gi.make_weights(case["wseed"], case["wscale"], in_chan=in_chan, lookback=case.get("lookback", 1), obj_px=obj_px)
+    assert tuple(m.feature_space_dim) == (net["n_features"], G, G), m.feature_space_dim
+    w = gi.make_weights(case["wseed"], case["wscale"], in_chan=in_chan, lookback=case.get("lookback", 1), obj_px=obj_px, **net)
     m.load_state_dict({k: torch.from_numpy(v) for k, v in w.items()}, strict=True)
 
     x = gi.make_image(100 + case["wseed"], B, I, case["max_objects"], in_chan=in_chan)

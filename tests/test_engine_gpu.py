@@ -8,68 +8,16 @@ import pytest
 import torch
 
 import golden_inputs as gi
-from helpers import KL_NAMES, load_case
+from helpers import assert_fp32_step_matches, build_model, load_case
 
 pytestmark = pytest.mark.gpu
-
-
-def build_model(case, dtype):
-    from spair_pytorch_amd import config as cfg
-    from spair_pytorch_amd.models import SPAIR
-    cfg.set_grid(case["I"], case["strides"])
-    m = SPAIR([1, case["I"], case["I"]], None, torch.device("cuda"), compute_dtype=dtype).to("cuda")
-    w = gi.make_weights(case["wseed"], case["wscale"])
-    m.load_state_dict({k: torch.from_numpy(v) for k, v in w.items()})
-    return m
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-12))
 
 
 @pytest.mark.parametrize("name", list(gi.CASES))
 def test_fp32_step_matches_reference(name):
     z, case = load_case(name)
     m = build_model(case, "f32")
-    x = torch.from_numpy(z["x"]).cuda()
-    noise = {k: torch.from_numpy(z[k]).cuda() for k in ("eps_box", "eps_attr", "eps_depth", "u_pres")}
-    m.zero_grad()
-    loss, recon, z_where, z_pres = m(x, int(z["global_step"]), noise=noise)
-    t = m.loss_terms().cpu().numpy()
-    assert abs(t[0] - float(z["loss"])) <= 2e-5 * abs(float(z["loss"]))
-    assert abs(t[1] - float(z["recon_loss"])) <= 2e-5 * float(z["recon_loss"])
-    for i, n in enumerate(KL_NAMES):
-        ref = float(z["kl_" + n])
-        assert abs(t[2 + i] - ref) <= 1e-4 * abs(ref) + 1e-4, (n, t[2 + i], ref)
-    assert rel(z_where.cpu().numpy(), z["z_where"]) < 1e-4
-    assert rel(z_pres.cpu().numpy(), z["z_pres"]) < 1e-4
-    assert rel(recon.cpu().numpy(), z["recon_x"]) < 2e-4
-    assert rel(m.export_map(0).cpu().numpy(), z["z_attr"]) < 1e-4
-    assert rel(m.export_map(1).cpu().numpy(), z["z_depth"]) < 1e-4
-    for i, n in enumerate(KL_NAMES[:6]):
-        assert rel(m.dist_param[n]["mean"].cpu().numpy(), z["mean_" + n]) < 1e-4, n
-        assert rel(m.dist_param[n]["sigma"].cpu().numpy(), z["sigma_" + n]) < 1e-4, n
-    loss.backward(retain_graph=True)
-    bad = []
-    for k, p in m.named_parameters():
-        if k.startswith("attn."):
-            assert p.grad is None
-            continue
-        g = p.grad.cpu().numpy()
-        gn = float(np.sqrt((g.astype(np.float64) ** 2).sum()))
-        ref_n = float(z["gradnorm_" + k])
-        if abs(gn - ref_n) > 2e-3 * ref_n + 1e-6:
-            bad.append((k, gn, ref_n))
-            continue
-        if ("grad_" + k) in z:
-            if np.abs(g - z["grad_" + k]).max() > 2e-3 * np.abs(z["grad_" + k]).max() + 1e-6:
-                bad.append((k, "elements"))
-        else:
-            smp = g.reshape(-1)[z["gradidx_" + k]]
-            if np.abs(smp - z["gradsample_" + k]).max() > 2e-3 * np.abs(z["gradsample_" + k]).max() + 1e-6:
-                bad.append((k, "samples"))
-    assert not bad, bad
+    assert_fp32_step_matches(m, z, retain_graph=True)
 
 
 # Per-case bounds of the bf16 step against the reference's fixtures.  Evidence: profiles/r04_bf16_parity_table.txt (tools/bf16_parity_table.py,

@@ -10,8 +10,9 @@ from oracle import spair_oracle as orc
 
 # c4 (32x32 grid, 1024 sequential cells) is the slow one: ~1 min
 # (the N_LOOKBACK = 2 / 3 fixtures pin the generalised context gather, the rgb_* ones the C = 3 channel plumbing, the p* ones object sizes
-# other than 28 px)
-CASES = list(gi.CASES) + list(gi.LOOKBACK_CASES) + list(gi.RGB_CASES) + list(gi.OBJ_CASES)
+# other than 28 px, the t_* ones other backbone topologies and feature / passthrough widths -- which also licenses the oracle as the expected
+# value of the N_ATTRIBUTES != 50 cases the reference cannot run, tests/test_topology_gpu.py)
+CASES = list(gi.CASES) + list(gi.LOOKBACK_CASES) + list(gi.RGB_CASES) + list(gi.OBJ_CASES) + list(gi.TOPO_CASES)
 
 
 def rel(a, b):
