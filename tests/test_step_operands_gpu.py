@@ -106,9 +106,10 @@ import math
 import pytest
 import torch
 
+from f64_hold import U, Record, _bias_sensitivity, _sensitivity, check_out, d64, gate_of, lin_wgrad, rne16
+
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -12           # the accumulation bound's factor
 STEP = 3000              # past the training wheel
 S2 = (2, 2, 2, 1, 1, 1)
 
@@ -157,16 +158,6 @@ def edge_stem(m):
 TWEAKS = {"F_edge_act0": edge_stem}
 
 
-def rne16(t):
-    """float64 -> bf16, round to nearest even (through fp32: the double rounding only moves a value within 2^-24 of its magnitude, far inside
-    every bound below)."""
-    return t.float().to(torch.bfloat16)
-
-
-def d64(t):
-    return t.double()
-
-
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # the step
 # ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -208,82 +199,9 @@ def run_step(name):
     return m, e["dims"], plan, views, V, Vp
 
 
-class Record:
-    def __init__(self, name):
-        self.name, self.ratio, self.bad, self.notes = name, {}, [], []
-        self.covered = set()          # parameters whose gradient was checked
-
-    def ratio_max(self, key, r):
-        self.ratio[key] = max(self.ratio.get(key, 0.0), float(r))
-        if not r <= 1.0:
-            self.bad.append((key, float(r)))
-
-    def fail(self, key, what):
-        self.bad.append((key, what))
-
-    def report(self):
-        print("\n[%s]" % self.name)
-        for k, r in self.ratio.items():
-            print("  %-46s %.3g" % (k, r))
-        for n in self.notes:
-            print("  " + n)
-
-
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # (a) weight gradients
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-def _sensitivity(rec, key, ref, bound, drop):
-    """The bound must reject the reference with 1/32 of its rows removed (`drop`: their contribution) and with its 8-column blocks shifted by
-    one block (column j read from j + 8; a matrix of fewer than 16 columns -- a grey 3x3 stem's 9 -- has no second block: the rows only)."""
-    c = ref.shape[1] // 8 * 8 - 8
-    r_drop = float((drop.abs() / bound).max())
-    r_shift = float(((ref[:, 8:8 + c] - ref[:, 0:c]).abs() / bound[:, 0:c]).max()) if c > 0 else math.inf
-    if not (r_drop > 1 and r_shift > 1):
-        rec.fail(key, "vacuous bound (drop %.3g, shift %.3g)" % (r_drop, r_shift))
-
-
-def _bias_sensitivity(rec, key, ref, bound, drop):
-    """The same for a bias bound (a vector): the dropped rows always, the shifted 8-element block where the bias has 16 elements or more
-    (the heads' 1, 2 and 8 have no second block)."""
-    r_drop = float((drop.abs() / bound).max())
-    c = ref.numel() // 8 * 8 - 8
-    r_shift = float(((ref[8:8 + c] - ref[0:c]).abs() / bound[0:c]).max()) if c > 0 else math.inf
-    if not (r_drop > 1 and r_shift > 1):
-        rec.fail(key, "vacuous bound (drop %.3g, shift %.3g)" % (r_drop, r_shift))
-
-
-def lin_wgrad(rec, key, grad_w, grad_b, dY, X, round_ops, chunk=16384):
-    """grad_w[out, in] = sum_r dY[r, out] X[r, in], grad_b = sum_r dY[r, :] in float64 (GPU), against the kernel's."""
-    R = dY.shape[0]
-    rdrop = R // 32          # one row split's worth of rows (1/32), from the middle: rows R/2 ..
-    ra = R // 2
-    acc = torch.zeros(dY.shape[1], X.shape[1], dtype=torch.float64, device=dY.device)
-    absb, drop = torch.zeros_like(acc), torch.zeros_like(acc)
-    bsum = torch.zeros(dY.shape[1], dtype=torch.float64, device=dY.device)
-    babs, bdrop = torch.zeros_like(bsum), torch.zeros_like(bsum)
-    for r0 in range(0, R, chunk):
-        a, b = dY[r0:r0 + chunk], X[r0:r0 + chunk]
-        a32 = d64(a)            # (the bias gradient sums dY as loaded, before any rounding: gemm.hip's column sums)
-        if round_ops:
-            a, b = a.to(torch.bfloat16), b.to(torch.bfloat16)
-        a, b = d64(a), d64(b)
-        acc += a.T @ b
-        absb += a.abs().T @ b.abs()
-        bsum += a32.sum(0)
-        babs += a32.abs().sum(0)
-        d0, d1 = max(ra - r0, 0), min(ra + rdrop - r0, a.shape[0])
-        if d1 > d0:
-            drop += a[d0:d1].T @ b[d0:d1]
-            bdrop += a32[d0:d1].sum(0)
-    bound = U * absb + 1e-30
-    rec.ratio_max(key + ".weight", ((d64(grad_w) - acc).abs() / bound).max())
-    _sensitivity(rec, key + ".weight", acc, bound, drop)
-    bb = U * babs + 1e-30
-    rec.ratio_max(key + ".bias", ((d64(grad_b) - bsum).abs() / bb).max())
-    _bias_sensitivity(rec, key + ".bias", bsum, bb, bdrop)
-    rec.covered |= {key + ".weight", key + ".bias"}
-
-
 def conv_taps(X, k, s, ho, wo):
     """The (ky, kx) tap views of NHWC input X for a k x k / stride-s valid convolution with an ho x wo output."""
     for ky in range(k):
@@ -401,57 +319,6 @@ def stem_wgrad_from_recomputed_dact0(rec, key, grad_w, grad_b, dact1, act0, W1, 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # (b) activations and data gradients
 # ---------------------------------------------------------------------------------------------------------------------------------------------
-def gate_of(a):
-    """The ReLU gate of a data gradient from the stored activation a: a > 0.  -0.0 and +0.0 are off, a positive bf16 denormal is on --
-    whether the kernel reads the value or the sign bits its forward left.  Also returns how many of each the data holds."""
-    neg0 = int(((a == 0) & torch.signbit(a)).sum())
-    den = int(((a != 0) & (a.abs() < 2.0 ** -126)).sum())
-    return a > 0, neg0, den
-
-
-def check_out(rec, key, got, ref, beta, relu=False, gate=None, part=None):
-    """A bf16 output must lie in [RNE(f(ref - beta)), RNE(f(ref + beta))] (f: the ReLU where the kernel applies one; RNE is monotone, so
-    this is 'RNE of the float64 value, either neighbour only within beta of a rounding boundary'); an fp32 output within beta + 2^-24 |ref|.
-    gate: (mask, -0.0 count, denormal count) of gate_of; where the mask is False the output must be exactly 0.  Sensitivity: the accepted
-    set must exclude the reference with its channels shifted by one 8-column block (channel j read from j + 8) and, where `part` is given
-    (the contribution of one block of 8 summed input channels), the reference without that block."""
-    f = (lambda t: t.clamp_min(0)) if relu else (lambda t: t)
-    note = ""
-    if gate is not None:
-        mask, neg0, den = gate
-        ref, beta = ref * mask, beta * mask
-        part = part * mask if part is not None else None
-        off = ~mask
-        if bool((got[off] != 0).any()):
-            rec.fail(key, "%d gated-off elements are not 0" % int((got[off] != 0).sum()))
-        note = "; gate read %d -0.0 and %d bf16-denormal activations" % (neg0, den)
-    shifted = ref.clone()
-    shifted[..., :-8] = ref[..., 8:]
-    wrong = [("shift", shifted)] + ([("drop", ref - part)] if part is not None else [])
-    if got.dtype == torch.bfloat16:
-        lo, hi = rne16(f(ref - beta)).double(), rne16(f(ref + beta)).double()
-        g = d64(got)
-        bad = (g < lo) | (g > hi)
-        nbad = int(bad.sum())
-        near = int((got != rne16(f(ref))).sum())
-        if nbad:
-            rec.fail(key, "%d bf16 elements outside [RNE(ref - beta), RNE(ref + beta)]" % nbad)
-        for what, w in wrong:
-            r = rne16(f(w)).double()
-            if not bool(((r < lo) | (r > hi)).any()):
-                rec.fail(key, "vacuous bound (%s)" % what)
-        rec.notes.append("%s: %d of %d elements differ from RNE(ref), all within beta of a rounding boundary%s" % (key, near, got.numel(), note)
-                         if not nbad else "%s: %d elements outside" % (key, nbad))
-    else:
-        bound = beta + 2.0 ** -24 * ref.abs() + 1e-30
-        rec.ratio_max(key, ((d64(got) - f(ref)).abs() / bound).max())
-        for what, w in wrong:
-            if not float(((f(w) - f(ref)).abs() / bound).max()) > 1:
-                rec.fail(key, "vacuous bound (%s)" % what)
-        if note:
-            rec.notes.append(key + note)
-
-
 def conv_fwd64(X, W, bias, k, s, ho, wo):
     """The valid convolution in float64, the sum of its absolute terms, and the contribution of the 8 input channels from ci / 2 on."""
     co = W.shape[0]
