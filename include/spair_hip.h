@@ -373,6 +373,17 @@ int spair_stem_conv_fwd(const float* x, const float* w, const float* bias, void*
  * column ((class * 2 + half) * 4 + tap) * 64 + c holds W[o][ci = half * 64 + c][ky = py + 2 dy][kx = px + 2 dx], class = 2 py + px, tap = 2 dy + dx;
  * out16 [B * Hout * Hout][128].  Returns SPAIR_ERR_UNSUPPORTED when a 256-row tile's input patch exceeds the kernel's LDS buffer. */
 int spair_conv_s2k4_fwd16(const void* in16, const void* wf16, const float* bias, void* out16, int B, int Hin, int Hout, void* stream);
+/* The same launch leaving, beside its output, the sign-bit mask described below (mask8 [B * Hout * Hout][16] bytes, bit e of byte g =
+ * channel 8 g + e of the stored bf16 output > 0): what the training step runs where the next layer's data gradient reads its gate as bits.
+ * The output is bit-identical to spair_conv_s2k4_fwd16's.  SPAIR_ERR_SHAPE for a NULL mask8. */
+int spair_conv_s2k4_fwd16_mask(const void* in16, const void* wf16, const float* bias, void* out16, void* mask8, int B, int Hin, int Hout,
+                               void* stream);
+/* The tiling the two patch-resident launchers choose -- the very code they run, host arithmetic only (no device is needed, nothing is
+ * launched).  dgrad = 0: spair_conv_s2k4_fwd16 with H = Hout (tiles of 256 output pixels); dgrad = 1: spair_conv_s2k4_dgrad16 / _bits with
+ * H = Ho (tiles of 128 pixels of one output-parity class grid, (Ho + 1)^2 per image; the launch is persistent, min(tiles, CUs) workgroups).
+ * Writes *tiles and *tpi (tiles per image when every tile restarts at an image, 0 when the tiles run over the whole batch) and returns
+ * SPAIR_OK, or SPAIR_ERR_UNSUPPORTED where the launcher refuses the shape. */
+int spair_conv_s2k4_tiling(int dgrad, int B, int H, int* tiles, int* tpi);
 /* Patch-resident DATA GRADIENT of the same layers (csrc/conv_s2_dgrad.hip): dout16 bf16 NHWC [B][Ho][Ho][128]; wdq: bf16 [128 ci][4 * 128], column
  * (ty * 2 + tx) * 128 + co = W[co][ci][py + 2 ty][px + 2 tx] for output-parity class q = 2 py + px; gate16: the stored activation of the layer
  * below, bf16 NHWC [B][2 (Ho + 1)][2 (Ho + 1)][128]; out16 (same shape) = conv2d_backward_input(dout, W) where gate16 > 0, else 0. */

@@ -14,6 +14,9 @@ int conv_s2k4_patch_fwd16(const void* in, const void* wf, const float* bias, voi
 // gradient fused (stem_part != nullptr: nothing is stored to `out`; _stem_supported); gate_bits != nullptr: the gate as sign bits, one byte
 // per (pixel, 8 channels) -- what the stem kernel (misc.hip) or the patch forward leaves -- instead of the activation itself
 bool conv_s2k4_patch_dgrad16_supported(int B, int Ho, int hin, int cin, int cout, int k, int s_);
+// the tiling of the 128 -> 128 channel data gradient alone (tiles of 128 class pixels; tpi: tiles per image, 0 = whole-batch tiles), or false:
+// the part of the launcher's geometry check that needs no device (the persistent grid = min(tiles, CUs) is chosen at the launch)
+bool conv_s2k4_patch_dgrad16_tiling(int B, int Ho, int& tiles, int& tpi);
 bool conv_s2k4_patch_dgrad16_stem_supported(int B, int Ho, int hin, int cin, int cout, int k, int s_, int stem_hin, int stem_s, long long stem_part_cap);
 int conv_s2k4_patch_dgrad16(const void* dout, const void* const* wd, const void* gate, void* out, int B, int Ho, int hin, int cin, int cout, int k,
                             int s_, const float* stem_xp, int stem_hin, int stem_s, float* stem_part, long long stem_part_cap, float* stem_dw,

@@ -257,3 +257,18 @@ int conv_s2k4_patch_fwd16(const void* in, const void* wf, const float* bias, voi
 extern "C" int spair_conv_s2k4_fwd16(const void* in16, const void* wf16, const float* bias, void* out16, int B, int Hin, int Hout, void* stream) {
     return conv_s2k4_patch_fwd16(in16, wf16, bias, out16, B, Hin, Hout, 128, 128, 4, 2, (hipStream_t)stream);
 }
+// the same launch leaving the sign-bit mask of its output beside it (mask8 [B*Hout*Hout][16] bytes: conv_2's data-gradient gate in the step)
+extern "C" int spair_conv_s2k4_fwd16_mask(const void* in16, const void* wf16, const float* bias, void* out16, void* mask8, int B, int Hin, int Hout,
+                                          void* stream) {
+    if (!mask8) return SPAIR_ERR_SHAPE;
+    return conv_s2k4_patch_fwd16(in16, wf16, bias, out16, B, Hin, Hout, 128, 128, 4, 2, (hipStream_t)stream, mask8);
+}
+// the tiling the two patch-resident launchers choose (cp_plan; conv_s2_dgrad.hip's dg_tiling): host arithmetic only, no device is asked
+extern "C" int spair_conv_s2k4_tiling(int dgrad, int B, int H, int* tiles, int* tpi) {
+    if (!tiles || !tpi) return SPAIR_ERR_SHAPE;
+    int t = 0, p = 0;
+    if (dgrad) { if (!conv_s2k4_patch_dgrad16_tiling(B, H, t, p)) return SPAIR_ERR_UNSUPPORTED; }
+    else { const int rc = cp_plan(B, 2 * H + 2, H, CP_C, CP_C, 4, 2, t, p); if (rc != SPAIR_OK) return rc; }
+    *tiles = t; *tpi = p;
+    return SPAIR_OK;
+}

@@ -351,10 +351,9 @@ __global__ __launch_bounds__(768, 3) void k_conv_s2k4_dgrad(ConvDgradArgs a) {
 
 int spair_stem_fused_reduce(float* part, int nblk, float* dw, float* db, hipStream_t s);      // gemm16.hip
 
-// geometry and scratch check shared by the launcher and the _supported predicates: the tiling (tpi: tiles per image, 0 = whole-batch tiles) and
-// the persistent grid, or false.  stem: one [128][17] partial per workgroup in stem_part_cap floats, an even stem input side and stride.
-static bool dg_plan(int B, int Ho, int hin, int cin, int cout, int k, int s_, bool stem, int stem_hin, int stem_s, long long stem_part_cap,
-                    int& tpi_out, int& grid_out) {
+// the tiling part of the geometry check, host arithmetic only (no device is asked): the number of 128-pixel tiles and tpi (tiles per image,
+// 0 = whole-batch tiles), or false.  Shared by dg_plan below and the tiling query spair_conv_s2k4_tiling (conv_s2.hip).
+static bool dg_tiling(int B, int Ho, int hin, int cin, int cout, int k, int s_, int& tiles_out, int& tpi_out) {
     const int Hc = Ho + 1;
     if (cin != DG_C || cout != DG_C || k != 4 || s_ != 2 || hin != 2 * Hc || B <= 0 || Ho <= 0) return false;
     const long long M = (long long)B * Hc * Hc;
@@ -378,6 +377,16 @@ static bool dg_plan(int B, int Ho, int hin, int cin, int cout, int k, int s_, bo
         if (worst > DG_PPX) return false;
         tiles = B * tpi;
     }
+    tiles_out = tiles; tpi_out = tpi;
+    return true;
+}
+bool conv_s2k4_patch_dgrad16_tiling(int B, int Ho, int& tiles, int& tpi) { return dg_tiling(B, Ho, 2 * (Ho + 1), DG_C, DG_C, 4, 2, tiles, tpi); }
+// geometry and scratch check shared by the launcher and the _supported predicates: the tiling and the persistent grid, or false.  stem: one
+// [128][17] partial per workgroup in stem_part_cap floats, an even stem input side and stride.
+static bool dg_plan(int B, int Ho, int hin, int cin, int cout, int k, int s_, bool stem, int stem_hin, int stem_s, long long stem_part_cap,
+                    int& tpi_out, int& grid_out) {
+    int tiles = 0, tpi = 0;
+    if (!dg_tiling(B, Ho, hin, cin, cout, k, s_, tiles, tpi)) return false;
     const int grid = std::min(tiles, spair_num_cus());      // persistent: one 160-KB workgroup per CU walks the tiles
     if (stem && ((long long)grid * DG_STEM_FLOATS > stem_part_cap || (stem_hin & 1) || (stem_s & 1))) return false;
     tpi_out = tpi; grid_out = grid;
