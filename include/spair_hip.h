@@ -479,6 +479,28 @@ int spair_render_layers(const SpairDims* d, const void* workspace, int flags, co
 int spair_render_layers_rows(const void* sprites, int ld_s, int s16, int ch, const float* nbox, const float* pres, const float* depth,
                              const int* cidx, const int* cells, int K, const float* inv_den, float* layers, float* layer_weight, int B,
                              int HW, int I, int Iw, int P, int align_corners, void* stream);
+/* ---- scene generation: latents drawn from the model's own prior (csrc/prior.hip; the generative process the loss assumes, reference
+ * models.py:169-262).  Cells in row-major order i = h * Gw + w, HW = G * Gw <= 1024.
+ * spair_prior_presence (unit level, no model): u [B][HW] uniform draws in [0, 1) -> z_pres [B][HW] (hard: 0.0 or 1.0), p_z [B][HW],
+ *   n_present int32 [B] = the sum of z_pres.  With cd the distribution of the object count c = 0 .. HW, started from
+ *   normalise((1 - count_prior_prob) count_prior_prob^c), `seen` the objects so far and rem = HW - i:
+ *       q_c = clamp(c - seen, 0, rem) / rem,  p_z(i) = sum_c cd_c q_c,  z_i = [u_i < p_z(i)],
+ *       cd <- cd (z_i q + (1 - z_i)(1 - q)) / max(its sum, 1e-6),  seen += z_i.
+ *   count != NULL (B device ints): sample b holds exactly n = clamp(count[b], 0, HW) objects, uniformly placed -- the same recursion from
+ *   the one-hot distribution at n, in closed form: p_z(i) = fl32((n - seen) / rem), correctly rounded (exactly 1 when n - seen == rem,
+ *   exactly 0 when n == seen); count_prior_prob is then not read.  One wave per sample, no atomics: bit-identical from run to run.
+ *   SPAIR_ERR_SHAPE before any launch for B < 1, HW < 1 or > 1024, a NULL u / z_pres / p_z / n_present, and, with count == NULL, a
+ *   count_prior_prob that is not strictly inside (0, 1) (NaN included).
+ * spair_prior_sample: the four noise maps of a step (eps_box [B][4][G][Gw], eps_attr [B][A][G][Gw], eps_depth / u_pres [B][1][G][Gw]) ->
+ *   z_where [B][4][G][Gw] = (xt, yt, xs, ys), z_what [B][A][G][Gw], z_depth [B][1][G][Gw] and z_pres / p_z [B][1][G][Gw], n_present [B] as
+ *   above.  The raw latent is prior_mean + prior_std * eps (SpairDims order cy, cx, height, width, attr, depth), then the step's own box
+ *   and depth transforms; z_what is the raw latent.  Reads no parameters, no workspace, no SpairStep.status; both kernels on `stream`.
+ *   What spair_compose takes. */
+int spair_prior_presence(const float* u, int B, int HW, float count_prior_prob, const int* count /* [B] or NULL */,
+                         float* z_pres, float* p_z, int* n_present, void* stream);
+int spair_prior_sample(const SpairDims* d, float count_prior_prob, const int* count,
+                       const float* eps_box, const float* eps_attr, const float* eps_depth, const float* u_pres,
+                       float* z_where, float* z_what, float* z_depth, float* z_pres, float* p_z, int* n_present, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,7 @@ def lib():
             f.argtypes, f.restype = args, ctypes.c_int
         _declare_parse(h)
         _declare_compose(h)
+        _declare_prior(h)
         _lib = h
     return _lib
 
@@ -101,6 +102,16 @@ def _declare_compose(h):
     h.spair_render_layers.argtypes = [ctypes.POINTER(SpairDims), vp, i, vp, i, vp, vp, vp, vp]
     h.spair_render_layers_rows.argtypes = [vp, i, i, i, vp, vp, vp, vp, vp, i, vp, vp, vp, i, i, i, i, i, i, vp]
     for fn in (h.spair_compose, h.spair_render_layers, h.spair_render_layers_rows):
+        fn.restype = i
+
+
+def _declare_prior(h):
+    """Argument lists of the scene-generation entry points (include/spair_hip.h, "scene generation"): a float by value, a 64-bit seed."""
+    vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    h.spair_prior_presence.argtypes = [vp, i, i, f, vp, vp, vp, vp, vp]
+    h.spair_prior_sample.argtypes = [ctypes.POINTER(SpairDims), f, vp] + [vp] * 11
+    h.spair_noise_fill.argtypes = [ctypes.POINTER(SpairDims), ctypes.c_uint64, vp, vp, vp, vp, vp]
+    for fn in (h.spair_prior_presence, h.spair_prior_sample, h.spair_noise_fill):
         fn.restype = i
 
 
@@ -214,3 +225,26 @@ def render_layers(sprites, channels, nbox, pres, depth, cells, inv_den, B, HW, I
                                          ptr(pres), ptr(depth), ptr(rows), ptr(cells), K, ptr(inv_den), ptr(layers), ptr(weight), int(B),
                                          int(HW), int(I), int(Iw), int(P), int(bool(align_corners)), stream()), "spair_render_layers_rows")
     return layers, weight
+
+
+def prior_presence(u, prob, count=None):
+    """spair_prior_presence on torch tensors: ``u`` fp32 [B,HW] uniform draws in [0, 1) on the device, ``prob`` the count prior's
+    probability (strictly inside (0, 1); not read when ``count`` is given), ``count`` None, an int or an int tensor [B]: that many
+    objects exactly, clamped to [0, HW].  Returns (z_pres fp32 [B,HW], hard; p_z fp32 [B,HW]; n_present int32 [B])."""
+    if not u.is_cuda or u.dim() != 2:
+        raise SpairHipError("prior_presence: u must be a [B,HW] tensor on the MI355X")
+    u = u.contiguous().float()
+    B, HW = (int(v) for v in u.shape)
+    dev = u.device
+    if count is not None:
+        if torch.is_tensor(count):
+            count = count.to(device=dev).clamp(-1, HW + 1).to(torch.int32).contiguous()
+        else:
+            count = torch.full((B,), max(-1, min(int(count), HW + 1)), device=dev, dtype=torch.int32)
+        if count.numel() != B:
+            raise SpairHipError("prior_presence: count must hold B values")
+    z = torch.empty(B, HW, device=dev, dtype=torch.float32)
+    pz = torch.empty(B, HW, device=dev, dtype=torch.float32)
+    n = torch.empty(B, device=dev, dtype=torch.int32)
+    check(lib().spair_prior_presence(ptr(u), B, HW, float(prob), ptr(count), ptr(z), ptr(pz), ptr(n), stream()), "spair_prior_presence")
+    return z, pz, n

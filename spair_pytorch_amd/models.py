@@ -146,6 +146,23 @@ class ComposeResult:
                                                for k in self.__slots__)
 
 
+class GenerateResult:
+    """What ``SPAIR.generate`` returns (device tensors; cell order k = h * Gw + w): the drawn latents ``z_where`` [B,4,G,Gw] = (xt, yt,
+    xs, ys), ``z_what`` [B,A,G,Gw], ``z_depth`` and ``z_pres`` [B,1,G,Gw] (``z_pres`` hard: 0.0 or 1.0), ``p_z`` [B,1,G,Gw]: the count
+    prior's probability of each cell given the cells before it; ``count`` int32 [B]: the number of present cells; and what ``compose``
+    returns on those latents: ``recon`` [B,C,I,Iw], ``boxes`` [B,G*Gw,4], ``layers`` / ``layer_weight`` (None without ``layers=``).
+    It qualifies as a ``scene`` of ``SPAIR.compose``."""
+    __slots__ = ("z_where", "z_what", "z_depth", "z_pres", "p_z", "count", "recon", "boxes", "layers", "layer_weight")
+
+    def __init__(self, **fields):
+        for k in self.__slots__:
+            setattr(self, k, fields[k])
+
+    def __repr__(self):
+        return "GenerateResult(%s)" % ", ".join("%s=%s" % (k, None if getattr(self, k) is None else tuple(getattr(self, k).shape))
+                                                for k in self.__slots__)
+
+
 class _NullWriter:
     def __getattr__(self, name):
         return lambda *a, **k: None
@@ -667,6 +684,76 @@ class SPAIR(nn.Module):
                                                     L.ptr(out_layers), L.ptr(weight), L.stream()), "spair_render_layers")
             return ComposeResult(recon=recon, boxes=parse_boxes(lat["z_where"], I, Iw, bool(d.align_corners)), layers=out_layers,
                                  layer_weight=weight)
+
+    def generate(self, batch, global_step=0, *, count=None, seed=None, noise=None, layers=None):
+        """Sample ``batch`` scenes from the model's own prior -- the generative process the loss assumes -- and render them: latents drawn by
+        ``spair_prior_sample``, then ``compose``.  Returns a ``GenerateResult``.
+
+        Gaussian latents: raw = m + s * eps with (m, s) of ``cfg.PRIORS`` (cy, cx, height, width, attr, depth), then the forward's own
+        transforms: cell_y/x = (MAX_YX - MIN_YX) sigmoid(clamp10(raw)) + MIN_YX, height/width likewise with MIN_HW / MAX_HW,
+        z_where = (xt, yt, xs, ys) = (cell_px / Iw (cell_x + w), cell_px / I (cell_y + h), width anchor / Iw, height anchor / I),
+        z_what = raw, z_depth = 4 sigmoid(clamp10(raw)).  The training wheel plays no part.
+
+        Presence: the sequential count prior of the KL (reference models.py:184-257), cells in row-major order.  The count distribution
+        starts from normalise((1 - p) p^c), c = 0 .. G*Gw, with p the count-prior probability of ``global_step`` (the schedule ``forward``
+        uses: almost flat over 0 .. G*Gw at step 0, p ~ 0.012 late); cell i gets p_z(i) = sum_c cd_c clamp(c - seen, 0, rem) / rem with
+        rem = G*Gw - i, and z_pres = [u < p_z] is HARD (0.0 or 1.0), which is what the recursion conditions on.
+
+        ``count``: None, an int or an int tensor [B] on the device: exactly that many objects per sample, uniformly placed (the same
+        recursion from a one-hot count distribution, p_z = (count - seen) / rem exactly).  A value outside [0, G*Gw] is clamped (in the
+        kernel: the host does not synchronise to validate it).
+
+        ``noise``: the dict ``forward`` takes (eps_box / eps_attr / eps_depth / u_pres, NCHW maps of batch size ``batch``; u_pres in
+        [0, 1)); it wins over ``seed``.  ``seed=int`` fills fresh maps from that seed and touches NO torch generator, so it is safe inside
+        a training run; ``seed=None`` draws the seed from torch's CPU generator as ``forward`` does (``torch.manual_seed`` controls it).
+        The maps are tensors of this call, not the engine's.
+
+        Everything after the latents IS ``self.compose(...)`` (``layers`` is passed through): ``no_grad``, no loss, the step-status word
+        ``FusedAdam`` reads is NOT written, so it is safe between ``backward()`` and ``FusedAdam.step()``; like ``compose`` it advances the
+        engine generation of that batch size (``backward()`` of an earlier forward of the same batch size raises afterwards)."""
+        self._ensure_ready()
+        B = int(batch)
+        if B < 1:
+            raise AssertionError("generate: batch must be >= 1, got %r" % (batch,))
+        e = self._engine(B)
+        d = e['dims']
+        (G, A), Gw = (d.G, d.A), dims_width(d)[1]
+        dev = self.device
+        want = {k: tuple(v.shape) for k, v in e['noise'].items()}      # [B,{4,A,1,1},Gh,Gw]
+        lib = L.lib()
+        if noise is not None:
+            noise = {k: noise[k].to(dev).contiguous().float() for k in NOISE_MAPS}
+            for k, v in noise.items():
+                if tuple(v.shape) != want[k]:
+                    raise AssertionError("noise[%r]: expected %s, got %s" % (k, want[k], tuple(v.shape)))
+        else:
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            noise = {k: torch.empty(want[k], device=dev, dtype=torch.float32) for k in NOISE_MAPS}
+            L.check(lib.spair_noise_fill(ctypes.byref(d), int(seed) & (2 ** 64 - 1), *(L.ptr(noise[k]) for k in NOISE_MAPS), L.stream()),
+                    "spair_noise_fill")
+        cnt = None
+        if count is not None:
+            if torch.is_tensor(count):
+                if not count.is_cuda:
+                    raise L.SpairHipError("generate: count must be an int or an int tensor on the MI355X")
+                if tuple(count.shape) != (B,) or count.is_floating_point():
+                    raise AssertionError("generate: count: expected an int tensor [%d], got %s %s" % (B, count.dtype, tuple(count.shape)))
+                cnt = count.clamp(-1, G * Gw + 1).to(torch.int32).contiguous()
+            else:
+                cnt = torch.full((B,), max(-1, min(int(count), G * Gw + 1)), device=dev, dtype=torch.int32)
+        st = step_scalars(global_step, B, self.world_size, False)
+        with torch.no_grad():
+            z_where = torch.empty(B, 4, G, Gw, device=dev, dtype=torch.float32)
+            z_what = torch.empty(B, A, G, Gw, device=dev, dtype=torch.float32)
+            z_depth, z_pres, p_z = (torch.empty(B, 1, G, Gw, device=dev, dtype=torch.float32) for _ in range(3))
+            n_present = torch.empty(B, device=dev, dtype=torch.int32)
+            L.check(lib.spair_prior_sample(ctypes.byref(d), float(st.count_prior_prob), L.ptr(cnt), *(L.ptr(noise[k]) for k in NOISE_MAPS),
+                                           L.ptr(z_where), L.ptr(z_what), L.ptr(z_depth), L.ptr(z_pres), L.ptr(p_z), L.ptr(n_present),
+                                           L.stream()), "spair_prior_sample")
+            r = self.compose(z_where=z_where, z_what=z_what, z_depth=z_depth, z_pres=z_pres, layers=layers)
+        return GenerateResult(z_where=z_where, z_what=z_what, z_depth=z_depth, z_pres=z_pres, p_z=p_z, count=n_present, recon=r.recon,
+                              boxes=r.boxes, layers=r.layers, layer_weight=r.layer_weight)
 
     def cell_rows(self, batch=None):
         """The cell-to-row table of the workspace of batch size ``batch`` (default: the latest forward's), int32 [G*Gw]: the per-cell rows
