@@ -501,6 +501,36 @@ int spair_prior_presence(const float* u, int B, int HW, float count_prior_prob, 
 int spair_prior_sample(const SpairDims* d, float count_prior_prob, const int* count,
                        const float* eps_box, const float* eps_attr, const float* eps_depth, const float* u_pres,
                        float* z_where, float* z_what, float* z_depth, float* z_pres, float* p_z, int* n_present, void* stream);
+/* ---- evaluation: the loss of one forward per image, per cell and per pixel (csrc/evaluate.hip; reference models.py:169-262, 544-563).
+ * Cells in row-major order k = h * Gw + w, HW = G * Gw <= 1024; row r = (cidx ? cidx[k] : k) * B + b; element (r, col) of a per-row
+ * array p with leading dimension ld is p[r * ld + col].
+ *   kl_map [B][7][HW]: j = 0 .. 5 (cy, cx, height, width, attr, depth): z_pres 0.5 (vr + t1 - 1 - log vr), vr = (sd / s)^2,
+ *       t1 = ((mu - m) / s)^2 against the prior (m, s) of that latent, attr summed over its A elements;
+ *       j = 6: z (log(z + 1e-9) - log(p_z + 1e-9)) + (1 - z)(log(1 - z + 1e-9) - log(1 - p_z + 1e-9)) on the STORED p_z.
+ *   bce_map [B][I][Iw]: sum over the C channels of -(x max(log recon, -100) + (1 - x) max(log(1 - recon), -100))   (torch's clamp).
+ *   terms [B][9]: 0: bce + beta * (sum of 2 .. 8), 1: bce, 2 .. 8: the seven KLs of the sample -- nats per image, unscaled: the batch
+ *       scalars of spair_forward's loss_out are loss_out[1] = sum_b terms[b][1], loss_out[2 + j] = kl_scale * sum_b terms[b][2 + j].
+ * kl_map / bce_map may be NULL (not computed); on them map = (accumulate ? map : 0) + scale * value (one writer per element: K calls
+ * with scale = 1 / K, the first with accumulate = 0, leave the mean over K draws); terms is always written plainly.
+ * scratch: spair_sample_terms_scratch_floats(B, HW, I, Iw) floats (device), the per-workgroup partial sums; its size and the order of
+ * every sum depend on the shape alone.  No atomics: bit-identical from run to run.  Two launches on `stream`.
+ * spair_sample_terms_rows (unit level, no model, no workspace): the caller's arrays -- z_pres, p_z, mu_depth, sd_depth: one column;
+ *   mu_box / sd_box: four columns (cy, cx, height, width); mu_attr / sd_attr: A columns; cidx: HW device ints or NULL (identity);
+ *   prior_mean / prior_std: six HOST floats (cy, cx, height, width, attr, depth); recon, x [B][C][I][Iw].
+ * spair_eval_terms: the same on what the latest spair_forward left in `workspace` (its rows' z_pres, the p_z its count-prior KL stored,
+ *   the posterior means and standard deviations, the workspace's cell-to-row table, the priors of `d`); x that forward's image, recon
+ *   what it returned.  Writes nothing into the workspace.
+ * Both return SPAIR_ERR_SHAPE before any launch for a NULL mandatory pointer, B < 1, HW outside [1, 1024], A < 1 or A + 5 > 64, C < 1,
+ *   I < 1 or Iw < 1, a leading dimension below its column count. */
+long long spair_sample_terms_scratch_floats(int B, int HW, int I, int Iw);
+int spair_sample_terms_rows(const float* z_pres, int ld_z, const float* p_z, int ld_pz, const float* mu_box, int ld_mu_box,
+                            const float* sd_box, int ld_sd_box, const float* mu_attr, int ld_mu_attr, const float* sd_attr, int ld_sd_attr,
+                            const float* mu_depth, int ld_mu_depth, const float* sd_depth, int ld_sd_depth, const int* cidx,
+                            const float* prior_mean, const float* prior_std, float beta, const float* recon, const float* x, int B, int HW,
+                            int A, int C, int I, int Iw, float* terms, float* kl_map, float* bce_map, float* scratch, int accumulate,
+                            float scale, void* stream);
+int spair_eval_terms(const SpairDims* d, const void* workspace, int flags, const float* x, const float* recon, float beta, float* terms,
+                     float* kl_map, float* bce_map, float* scratch, int accumulate, float scale, void* stream);
 #ifdef __cplusplus
 }
 #endif

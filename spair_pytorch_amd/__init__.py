@@ -6,12 +6,12 @@ there is no PyTorch/CPU fallback.
 """
 from . import config  # noqa: F401
 
-__all__ = ["config", "SPAIR", "ParseResult", "ComposeResult", "GenerateResult", "parse_boxes"]
+__all__ = ["config", "SPAIR", "ParseResult", "ComposeResult", "GenerateResult", "EvalResult", "parse_boxes"]
 
 
 def __getattr__(name):
     # the model surface, resolved on first use (importing the package alone stays as light as it was: config only)
-    if name in ("SPAIR", "ParseResult", "ComposeResult", "GenerateResult", "parse_boxes"):
+    if name in ("SPAIR", "ParseResult", "ComposeResult", "GenerateResult", "EvalResult", "parse_boxes"):
         from . import models
         return getattr(models, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

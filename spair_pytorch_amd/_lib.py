@@ -81,6 +81,7 @@ def lib():
         _declare_parse(h)
         _declare_compose(h)
         _declare_prior(h)
+        _declare_evaluate(h)
         _lib = h
     return _lib
 
@@ -112,6 +113,17 @@ def _declare_prior(h):
     h.spair_prior_sample.argtypes = [ctypes.POINTER(SpairDims), f, vp] + [vp] * 11
     h.spair_noise_fill.argtypes = [ctypes.POINTER(SpairDims), ctypes.c_uint64, vp, vp, vp, vp, vp]
     for fn in (h.spair_prior_presence, h.spair_prior_sample, h.spair_noise_fill):
+        fn.restype = i
+
+
+def _declare_evaluate(h):
+    """Argument lists of the evaluation entry points (include/spair_hip.h, "evaluation"): floats by value, a 64-bit count returned."""
+    vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    h.spair_sample_terms_scratch_floats.argtypes = [i, i, i, i]
+    h.spair_sample_terms_scratch_floats.restype = ctypes.c_longlong
+    h.spair_sample_terms_rows.argtypes = [vp, i] * 8 + [vp, vp, vp, f, vp, vp] + [i] * 6 + [vp, vp, vp, vp, i, f, vp]
+    h.spair_eval_terms.argtypes = [ctypes.POINTER(SpairDims), vp, i, vp, vp, f, vp, vp, vp, vp, i, f, vp]
+    for fn in (h.spair_sample_terms_rows, h.spair_eval_terms):
         fn.restype = i
 
 
@@ -248,3 +260,46 @@ def prior_presence(u, prob, count=None):
     n = torch.empty(B, device=dev, dtype=torch.int32)
     check(lib().spair_prior_presence(ptr(u), B, HW, float(prob), ptr(count), ptr(z), ptr(pz), ptr(n), stream()), "spair_prior_presence")
     return z, pz, n
+
+
+def sample_terms(z_pres, p_z, mu_box, sd_box, mu_attr, sd_attr, mu_depth, sd_depth, priors, beta, recon, x, rows=None, maps=True,
+                 out=None, accumulate=False, scale=1.0):
+    """spair_sample_terms_rows on torch tensors.  Per-row operands: 2-D fp32 device tensors [N, cols] with N = HW * B rows
+    (row = rows[k] * B + b for cell k, ``rows`` an int32 [HW] tensor or None = identity) and unit stride along the columns -- a column
+    slice of a wider buffer is fine, its row stride is passed as the leading dimension; z_pres / p_z / mu_depth / sd_depth one column,
+    mu_box / sd_box four (cy, cx, height, width), mu_attr / sd_attr A.  ``priors``: six (mean, std).  recon, x fp32 [B,C,I,Iw].
+    Returns (terms [B,9], kl_map [B,7,HW] or None, bce_map [B,I,Iw] or None); ``out`` = such a triple to write into (with
+    ``accumulate`` / ``scale``: map = (accumulate ? map : 0) + scale * value)."""
+    ops = (z_pres, p_z, mu_box, sd_box, mu_attr, sd_attr, mu_depth, sd_depth)
+    for t in ops + (recon, x):
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise SpairHipError("sample_terms: fp32 tensors on the MI355X")
+    for t in ops:
+        if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise SpairHipError("sample_terms: per-row operands are [N, cols] with unit column stride")
+    recon, x = recon.contiguous(), x.contiguous()
+    B, C, I, Iw = (int(v) for v in x.shape)
+    A = int(mu_attr.shape[1])
+    HW = int(z_pres.shape[0]) // B
+    if any(int(t.shape[0]) != HW * B for t in ops) or tuple(recon.shape) != tuple(x.shape):
+        raise SpairHipError("sample_terms: inconsistent shapes")
+    dev = x.device
+    if rows is not None:
+        rows = rows.to(device=dev, dtype=torch.int32).contiguous()
+    if out is None:
+        out = (torch.empty(B, 9, device=dev), torch.empty(B, 7, HW, device=dev) if maps else None,
+               torch.empty(B, I, Iw, device=dev) if maps else None)
+    terms, kl_map, bce_map = out
+    n = int(lib().spair_sample_terms_scratch_floats(B, HW, I, Iw))
+    if n <= 0:
+        raise SpairHipError("sample_terms: unsupported shape (B=%d, HW=%d, image %dx%d)" % (B, HW, I, Iw))
+    scratch = torch.empty(n, device=dev, dtype=torch.float32)
+    pm = (ctypes.c_float * 6)(*(float(m) for m, _ in priors))
+    ps = (ctypes.c_float * 6)(*(float(s) for _, s in priors))
+    args = []
+    for t in ops:
+        args += [ptr(t), int(t.stride(0))]
+    check(lib().spair_sample_terms_rows(*args, ptr(rows), ctypes.cast(pm, ctypes.c_void_p), ctypes.cast(ps, ctypes.c_void_p), float(beta),
+                                        ptr(recon), ptr(x), B, HW, A, C, I, Iw, ptr(terms), ptr(kl_map), ptr(bce_map), ptr(scratch),
+                                        int(bool(accumulate)), float(scale), stream()), "spair_sample_terms_rows")
+    return terms, kl_map, bce_map

@@ -18,6 +18,7 @@
 #include "objconv.h"
 #include "render.h"
 #include "compose.h"
+#include "evaluate.h"
 
 #define TRY(expr)                      \
     do {                               \
@@ -1891,4 +1892,33 @@ extern "C" int spair_render_layers(const SpairDims* d0, const void* workspace, i
     const StepPlan p = plan_step(*d, flags, false, workspace);
     return render_layers(render_geom(*d, L, &w.cb), w.S, w.ld_s, p.rp.s16, d->C + 1, w.cidx, cells, K, inv_den, layers, layer_weight,
                          (hipStream_t)stream);
+}
+
+// ---- evaluation (evaluate.hip) ----------------------------------------------------------------------------------------
+// The loss of the latest spair_forward on this workspace per image, per cell and per pixel: the rows' z_pres, the p_z k_count_kl stored,
+// the posterior means and standard deviations (stat, Oe, sd_attr), walked in row-major cell order through the workspace's cell-to-row
+// table, against the priors of `d0`; recon is what that forward returned, x its image.  The operands are the same buffers for every step
+// plan (`flags` is taken for symmetry with the other entry points that read a forward's workspace).  Nothing of the workspace is written.
+extern "C" int spair_eval_terms(const SpairDims* d0, const void* workspace, int flags, const float* x, const float* recon, float beta,
+                                float* terms, float* kl_map, float* bce_map, float* scratch, int accumulate, float scale, void* stream) {
+    (void)flags;
+    if (!d0 || !workspace || !x || !recon || !terms || !scratch) return SPAIR_ERR_SHAPE;
+    const SpairDims dn = spair_dims_norm(*d0), *d = &dn;
+    if (d->B < 1 || d->G < 1 || d->Gw < 1 || (long long)d->G * d->Gw > EVAL_MAX_HW || d->A < 1 || d->A + 5 > 64 || d->I < 1 || d->Iw < 1)
+        return SPAIR_ERR_SHAPE;
+    TRY(validate(*d));
+    const CellLayout L = make_cell_layout(*d);
+    const Ws w = carve(*d, const_cast<void*>(workspace));
+    const CellBufs& P = w.cb;
+    EvalRows R;
+    R.z_pres = P.rec + (L.REC - 1); R.ld_z = L.ld_rec;
+    R.p_z = P.stat + ST_PZ; R.ld_pz = SP_LDSTAT;
+    R.mu_box = P.stat + ST_MU_BOX; R.sd_box = P.stat + ST_SD_BOX; R.ld_mu_box = R.ld_sd_box = SP_LDSTAT;
+    R.mu_attr = P.Oe; R.ld_mu_attr = L.ld_oe;
+    R.sd_attr = P.sd_attr; R.ld_sd_attr = L.ld_rec;
+    R.mu_depth = P.stat + ST_MU_DEPTH; R.sd_depth = P.stat + ST_SD_DEPTH; R.ld_mu_depth = R.ld_sd_depth = SP_LDSTAT;
+    R.cidx = w.cidx;
+    for (int i = 0; i < 6; ++i) { R.prior_mean[i] = d->prior_mean[i]; R.prior_std[i] = d->prior_std[i]; }
+    return eval_sample_terms(R, d->B, L.HW, d->A, d->C, d->I, d->Iw, beta, recon, x, terms, kl_map, bce_map, scratch, accumulate, scale,
+                             (hipStream_t)stream);
 }

@@ -163,6 +163,28 @@ class GenerateResult:
                                                 for k in self.__slots__)
 
 
+class EvalResult:
+    """What ``SPAIR.evaluate`` returns (device tensors; cell order k = h * Gw + w; nats per image, unscaled).
+
+    ``loss`` [B] = ``terms[:, 0]``: the negative single-sample ELBO of each image, BCE + VAE_BETA * (the seven KLs);
+    ``terms`` [B,9]: total, reconstruction BCE, KL cy, cx, height, width, attr, depth, presence -- the mean over the draws;
+    ``terms_draws`` [K,B,9]: the same per draw;
+    ``kl_map`` [B,7,G,Gw]: the seven KLs per cell, ``bce_map`` [B,I,Iw]: the BCE per pixel summed over the channels -- means over the
+    draws, None with ``maps=False``;
+    ``recon`` [B,C,I,Iw], ``z_where`` [B,4,G,Gw], ``z_pres`` [B,1,G,Gw] and ``loss_terms`` [9] (the batch scalars ``forward`` reports):
+    those of the LAST draw.  ``loss_terms[1] = terms[:, 1].sum()`` and ``loss_terms[2 + j] = terms[:, 2 + j].sum() / (B * world_size)``
+    for a single draw."""
+    __slots__ = ("loss", "terms", "terms_draws", "kl_map", "bce_map", "recon", "z_where", "z_pres", "loss_terms")
+
+    def __init__(self, **fields):
+        for k in self.__slots__:
+            setattr(self, k, fields[k])
+
+    def __repr__(self):
+        return "EvalResult(%s)" % ", ".join("%s=%s" % (k, None if getattr(self, k) is None else tuple(getattr(self, k).shape))
+                                            for k in self.__slots__)
+
+
 class _NullWriter:
     def __getattr__(self, name):
         return lambda *a, **k: None
@@ -754,6 +776,78 @@ class SPAIR(nn.Module):
             r = self.compose(z_where=z_where, z_what=z_what, z_depth=z_depth, z_pres=z_pres, layers=layers)
         return GenerateResult(z_where=z_where, z_what=z_what, z_depth=z_depth, z_pres=z_pres, p_z=p_z, count=n_present, recon=r.recon,
                               boxes=r.boxes, layers=r.layers, layer_weight=r.layer_weight)
+
+    def evaluate(self, x, global_step=0, *, samples=1, sample=True, seed=None, noise=None, maps=True):
+        """Score images under the model: the terms of the loss PER IMAGE, per cell and per pixel, as an ``EvalResult`` -- what
+        ``loss_terms()`` cannot give (nine batch scalars, the BCE summed over the batch, the KLs divided by B * world_size).  Per draw: one
+        ``no_grad`` forward, then ``spair_eval_terms`` on what it left in the workspace (kernel ``k_sample_terms``).
+
+        ``terms[b]`` = (BCE_b + VAE_BETA * sum of the KLs, BCE_b, KL cy, cx, height, width, attr, depth, presence) in nats, unscaled;
+        ``world_size`` plays no part in it.  The Gaussian KLs are masked by z_pres as in the loss; the presence KL uses the count prior's
+        p_z as the forward stored it, so ``global_step`` moves it (the count-prior schedule) and nothing else.  ``kl_map`` / ``bce_map``
+        say which cells spend the nats and which pixels carry the reconstruction error (``maps=False``: not computed).
+
+        Draws: ``samples=K`` averages K draws (``terms``, the maps; ``terms_draws`` keeps each).  ``sample=False`` is the posterior mean
+        (zero eps, u_pres = 0.5: constant maps) and needs ``samples == 1``.  ``noise`` is the dict ``forward`` takes, needs
+        ``samples == 1`` and wins over ``seed``.  ``seed=int`` fills noise maps of this call's own from that seed (draw k: ``seed + k``)
+        and touches NO torch generator, so it is safe inside a training run; ``seed=None`` draws one seed from torch's CPU generator as
+        ``forward`` does (``torch.manual_seed`` controls it), then behaves as ``seed=int``.
+
+        Like ``parse`` it overwrites the workspace of that batch size: ``backward()`` of an earlier forward of the same batch size raises
+        afterwards (the generation check).  And as any ``no_grad`` forward it rewrites the step-status word ``FusedAdam`` reads as its
+        skip flag: it must not be called between ``backward()`` and ``FusedAdam.step()``.  No gradients flow through it."""
+        self._ensure_ready()
+        if not x.is_cuda:
+            raise L.SpairHipError("input must be on the MI355X (got %s); there is no CPU path" % x.device)
+        x = x.contiguous().float()
+        if list(x.shape[1:]) != list(self.image_shape):
+            raise AssertionError("expected input [B,%s], got %s" % (self.image_shape, tuple(x.shape)))
+        K = int(samples)
+        if K < 1:
+            raise AssertionError("evaluate: samples must be >= 1, got %r" % (samples,))
+        if K > 1 and (noise is not None or not sample):
+            raise AssertionError("evaluate: samples > 1 needs drawn noise (noise= and sample=False describe one draw)")
+        if self.raise_on_nonfinite and self._status_host[0] != 0:
+            raise L.SpairHipError(self._status_text(self._status_host[0]) + " -- seen by a later evaluate(); clear_step_status() to go on")
+        e = self._engine(x.shape[0])
+        d = e['dims']
+        dev = x.device
+        lib = L.lib()
+        want = {k: tuple(v.shape) for k, v in e['noise'].items()}      # [B,{4,A,1,1},Gh,Gw]
+        own = None
+        if noise is not None:
+            noise = {k: noise[k].to(dev).contiguous().float() for k in NOISE_MAPS}
+            for k, v in noise.items():
+                if tuple(v.shape) != want[k]:
+                    raise AssertionError("noise[%r]: expected %s, got %s" % (k, want[k], tuple(v.shape)))
+        elif not sample:
+            noise = self._mean_noise(e)
+        else:
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            own = {k: torch.empty(want[k], device=dev, dtype=torch.float32) for k in NOISE_MAPS}
+        (B, G), (Iw, Gw) = (d.B, d.G), dims_width(d)
+        n_scratch = int(lib.spair_sample_terms_scratch_floats(B, G * Gw, d.I, Iw))
+        if n_scratch <= 0:
+            raise L.SpairHipError("evaluate: unsupported configuration (B=%d, %dx%d cells)" % (B, G, Gw))
+        with torch.no_grad():
+            draws = torch.empty(K, B, 9, device=dev, dtype=torch.float32)
+            kl_map = torch.empty(B, 7, G, Gw, device=dev, dtype=torch.float32) if maps else None
+            bce_map = torch.empty(B, d.I, Iw, device=dev, dtype=torch.float32) if maps else None
+            scratch = torch.empty(n_scratch, device=dev, dtype=torch.float32)
+            for k in range(K):
+                if own is not None:
+                    L.check(lib.spair_noise_fill(ctypes.byref(d), (int(seed) + k) & (2 ** 64 - 1), *(L.ptr(own[n]) for n in NOISE_MAPS),
+                                                 L.stream()), "spair_noise_fill")
+                    noise = own
+                terms, recon, z_where, z_pres = self._run_forward(x, int(global_step), noise, train=False)
+                L.check(lib.spair_eval_terms(ctypes.byref(d), L.ptr(e['workspace']), int(STEP_FLAGS), L.ptr(x), L.ptr(recon),
+                                             float(d.vae_beta), L.ptr(draws[k]), L.ptr(kl_map), L.ptr(bce_map), L.ptr(scratch),
+                                             int(k > 0), 1.0 / K, L.stream()), "spair_eval_terms")
+            self._loss_terms = terms
+            mean = draws.mean(0)
+            return EvalResult(loss=mean[:, 0], terms=mean, terms_draws=draws, kl_map=kl_map, bce_map=bce_map, recon=recon,
+                              z_where=z_where, z_pres=z_pres, loss_terms=terms[:9])
 
     def cell_rows(self, batch=None):
         """The cell-to-row table of the workspace of batch size ``batch`` (default: the latest forward's), int32 [G*Gw]: the per-cell rows
