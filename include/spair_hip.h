@@ -531,6 +531,31 @@ int spair_sample_terms_rows(const float* z_pres, int ld_z, const float* p_z, int
                             float scale, void* stream);
 int spair_eval_terms(const SpairDims* d, const void* workspace, int flags, const float* x, const float* recon, float beta, float* terms,
                      float* kl_map, float* bce_map, float* scratch, int accumulate, float scale, void* stream);
+/* ---- instance masks of the synthetic scenes (csrc/scenes.hip): spair_scenes_generate with one more output, mask int32 [B][I][I]:
+ * mask[b][y][x] = the index j of the glyph whose value at the pixel is largest (the lowest j on a tie), -1 where the pixel is 0.  image,
+ * bbox and count are bit for bit what spair_scenes_generate writes; mask >= 0 exactly where image > 0, and mask < count[b].  The same
+ * refusals, and SPAIR_ERR_SHAPE for a NULL mask, before any launch. */
+int spair_scenes_generate_masks(uint64_t seed, long long first, int B, int I, int K, int size_min, int size_max, float* image,
+                                float* bbox, long long* count, float* scratch, int* mask, void* stream);
+/* ---- segmentation metrics (csrc/segmentation.hip): a predicted label map scored against a true one, per image, on the device.
+ * pred [B][HW] in {-1, 0 .. NP-1}, truth [B][HW] in {-1, 0 .. K-1}; -1 is background, and so is every label outside its range.
+ *   contingency [B][NP+1][K+1] (written whole): n[i][j] = pixels with pred = i - 1 and truth = j - 1 (index 0: background); a_i its
+ *       row sums, b_j its column sums, N = HW, C2(v) = v (v - 1) / 2.
+ *   scores [B][5]:
+ *     0 ari:    (X - E) / (M - E) with X = sum C2(n_ij), E = sum C2(a_i) sum C2(b_j) / C2(N), M = (sum C2(a_i) + sum C2(b_j)) / 2;
+ *               1 where M = E (both partitions trivial, or N = 1);
+ *     1 ari_fg: the same on the columns j >= 1 (pixels of truth objects; background pred pixels are one cluster); NaN without such a pixel;
+ *     2 msc, 3 sc: with best_j = max over i >= 1 of n_ij / (a_i + b_j - n_ij) for every object j >= 1 with b_j > 0 (0 if no segment
+ *               meets it): their mean, and their mean weighted by b_j; NaN if no object has a pixel;
+ *     4 fg_iou: |pred >= 0 and truth >= 0| / |pred >= 0 or truth >= 0|, 1 if both are empty.
+ *   match [B][K] (may be NULL): the lowest predicted label attaining best_j > 0, else -1; match_iou [B][K] (may be NULL): best_j (0
+ *       for an object without pixels).  Candidates are compared by 64-bit cross-multiplication: no division decides a match.
+ * Sums are exact integers (the score numerators and denominators 128-bit), converted to double once and stored as fp32.  Integer
+ * atomics only: bit-identical from run to run.  A memset and two launches on `stream`; no allocation, no host synchronisation.
+ * SPAIR_ERR_SHAPE before any launch for B < 1, HW outside [1, 2^24], NP outside [1, 1024], K outside [1, 32], a NULL pred, truth,
+ * contingency or scores. */
+int spair_segmentation(const int* pred, const int* truth, int B, long long HW, int NP, int K, int* contingency, float* scores,
+                       int* match, float* match_iou, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,8 @@ there is no PyTorch/CPU fallback.
 """
 from . import config  # noqa: F401
 
-__all__ = ["config", "SPAIR", "ParseResult", "ComposeResult", "GenerateResult", "EvalResult", "parse_boxes"]
+__all__ = ["config", "SPAIR", "ParseResult", "ComposeResult", "GenerateResult", "EvalResult", "parse_boxes",
+           "segmentation", "SegmentationResult"]
 
 
 def __getattr__(name):
@@ -14,4 +15,7 @@ def __getattr__(name):
     if name in ("SPAIR", "ParseResult", "ComposeResult", "GenerateResult", "EvalResult", "parse_boxes"):
         from . import models
         return getattr(models, name)
+    if name in ("segmentation", "SegmentationResult"):
+        from . import metric
+        return getattr(metric, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -82,6 +82,7 @@ def lib():
         _declare_compose(h)
         _declare_prior(h)
         _declare_evaluate(h)
+        _declare_segmentation(h)
         _lib = h
     return _lib
 
@@ -124,6 +125,15 @@ def _declare_evaluate(h):
     h.spair_sample_terms_rows.argtypes = [vp, i] * 8 + [vp, vp, vp, f, vp, vp] + [i] * 6 + [vp, vp, vp, vp, i, f, vp]
     h.spair_eval_terms.argtypes = [ctypes.POINTER(SpairDims), vp, i, vp, vp, f, vp, vp, vp, vp, i, f, vp]
     for fn in (h.spair_sample_terms_rows, h.spair_eval_terms):
+        fn.restype = i
+
+
+def _declare_segmentation(h):
+    """Argument lists of the instance-mask and segmentation-metric entry points (include/spair_hip.h): 64-bit seed, first sample, HW."""
+    vp, i, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
+    h.spair_scenes_generate_masks.argtypes = [ctypes.c_uint64, ll, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
+    h.spair_segmentation.argtypes = [vp, vp, i, ll, i, i, vp, vp, vp, vp, vp]
+    for fn in (h.spair_scenes_generate_masks, h.spair_segmentation):
         fn.restype = i
 
 

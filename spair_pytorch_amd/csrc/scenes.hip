@@ -127,3 +127,47 @@ extern "C" int spair_scenes_generate(uint64_t seed, long long first, int B, int 
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }
+
+// ---- instance masks: the same scenes with the glyph that produced every pixel -------------------------------------------------------------
+namespace {
+
+// thread per pixel: k_scene_render's loop, keeping the glyph whose value is largest beside the value (strict >: the lowest j wins a tie;
+// -1 where no glyph is lit).  The image is formed by the same fmaxf chain, so it is bit-identical to k_scene_render's.
+__global__ __launch_bounds__(256) void k_scene_render_mask(const float* __restrict__ par, const long long* __restrict__ count, int B, int I, int K,
+                                                           float* __restrict__ image, int* __restrict__ mask) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)B * I * I) return;
+    const int x = (int)(idx % I), y = (int)((idx / I) % I), b = (int)(idx / ((long long)I * I));
+    const int k = (int)count[b];
+    float v = 0.f, top = 0.f;
+    int who = -1;
+    for (int j = 0; j < k; ++j) {
+        const float* o = par + ((size_t)b * K + j) * SC_OBJ;
+        const int y0 = (int)o[0], x0 = (int)o[1], size = (int)o[2], ns = (int)o[3];
+        if (y < y0 || y >= y0 + size || x < x0 || x >= x0 + size) continue;
+        const float ly = (float)(y - y0), lx = (float)(x - x0);
+        float g = 0.f;
+        for (int s = 0; s < ns; ++s) g = fmaxf(g, stroke_value(o + 4 + s * SC_STROKE, ly, lx));
+        v = fmaxf(v, g);
+        if (g > top) { top = g; who = j; }
+    }
+    image[idx] = v;
+    mask[idx] = who;
+}
+
+}  // namespace
+
+// spair_scenes_generate plus mask [B,I,I] int32: the index j of the glyph with the largest value at the pixel (lowest j on a tie), -1
+// where the image is 0.  Image, bbox and count are what spair_scenes_generate writes, bit for bit.
+extern "C" int spair_scenes_generate_masks(uint64_t seed, long long first, int B, int I, int K, int size_min, int size_max, float* image,
+                                           float* bbox, long long* count, float* scratch, int* mask, void* stream) {
+    if (B <= 0 || I <= 0 || K <= 0 || K > SC_MAXOBJ || size_min < 4 || size_max < size_min || !image || !bbox || !count || !scratch || !mask)
+        return SPAIR_ERR_SHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_scene_params, dim3(B), dim3(64), 0, s, seed, first, B, I, K, size_min, size_max, scratch, bbox, count);
+    SPAIR_CHECK_LAUNCH();
+    const long long total = (long long)B * I * I;
+    hipLaunchKernelGGL(k_scene_render_mask, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, scratch, count, B, I, K, image, mask);
+    SPAIR_CHECK_LAUNCH();
+    return SPAIR_OK;
+}

@@ -66,7 +66,10 @@ class DeviceScatteredDigits:
     """Batches of synthetic scenes generated on the GPU (csrc/scenes.hip): same item contract as SimpleScatteredMNISTDataset
     (dataloader.py:10-36) -- ``(image [B,1,I,I] float in [0,1], bbox [B,K,4] = (x, y, w, h) px zero padded, digit_count [B])`` -- but as
     device tensors, one launch pair per batch, deterministic in (seed, sample index).  Iterating yields ``len(self)`` batches per epoch;
-    ``batch(i)`` regenerates batch i of the stream directly (any rank, any epoch: rank r of W reads batches r, r+W, ...)."""
+    ``batch(i)`` regenerates batch i of the stream directly (any rank, any epoch: rank r of W reads batches r, r+W, ...);
+    ``batch(i, masks=True)`` also returns the scene's instance mask, int32 [B,I,I]: the index of the glyph (the row of ``bbox``) that
+    produced each pixel -- the one with the largest value there, the lowest index on a tie -- and -1 where the image is 0: the ground
+    truth ``metric.segmentation`` scores a parse against."""
 
     def __init__(self, n_samples, batch_size, image_side=128, max_objects=11, seed=1234, obj_px=(14, 28), device="cuda", rank=0, world=1):
         self.n, self.B, self.I, self.K, self.seed, self.obj_px = int(n_samples), int(batch_size), int(image_side), int(max_objects), int(seed), obj_px
@@ -76,7 +79,7 @@ class DeviceScatteredDigits:
     def __len__(self):
         return self.n // (self.B * self.world)
 
-    def batch(self, i, epoch=0):
+    def batch(self, i, epoch=0, masks=False):
         from . import _lib as L
         import ctypes
         if self.device.type != "cuda":
@@ -87,6 +90,12 @@ class DeviceScatteredDigits:
         cnt = torch.empty(self.B, dtype=torch.int64, device=self.device)
         if self._scratch is None:
             self._scratch = torch.empty(self.B * self.K * 28, device=self.device)
+        if masks:
+            mask = torch.empty(self.B, self.I, self.I, dtype=torch.int32, device=self.device)
+            L.check(L.lib().spair_scenes_generate_masks(ctypes.c_uint64(self.seed), ctypes.c_longlong(first), self.B, self.I, self.K,
+                                                        int(self.obj_px[0]), int(self.obj_px[1]), L.ptr(img), L.ptr(bbox), L.ptr(cnt),
+                                                        L.ptr(self._scratch), L.ptr(mask), L.stream()), "spair_scenes_generate_masks")
+            return img, bbox, cnt, mask
         L.check(L.lib().spair_scenes_generate(ctypes.c_uint64(self.seed), ctypes.c_longlong(first), self.B, self.I, self.K, int(self.obj_px[0]),
                                               int(self.obj_px[1]), L.ptr(img), L.ptr(bbox), L.ptr(cnt), L.ptr(self._scratch), L.stream()),
                 "spair_scenes_generate")
