@@ -556,6 +556,34 @@ int spair_scenes_generate_masks(uint64_t seed, long long first, int B, int I, in
  * contingency or scores. */
 int spair_segmentation(const int* pred, const int* truth, int B, long long HW, int NP, int K, int* contingency, float* scores,
                        int* match, float* match_iou, void* stream);
+/* ---- gradient norm and clipping by global L2 norm (csrc/gradnorm.hip; torch.nn.utils.clip_grad_norm_ in front of the Adam of
+ * train.py:44, which the reference itself never calls).  The norm is taken over SEGMENTS of the flat gradient buffer -- nseg ascending,
+ * non-overlapping, non-empty element ranges [seg_lo[s], seg_hi[s]), gaps allowed and never read -- cut into WORK ITEMS (segment, lo, hi) of at
+ * most SPAIR_GRAD_CHUNK consecutive floats inside one segment.  Every element is converted to float64 BEFORE it is squared and every
+ * sum is float64, so the norm of a buffer of 1e30s or of 1e-30s is its true norm, not inf or 0.  The order of every sum is fixed by
+ * the table and the buffer's address (per lane strided, a cross-lane tree, the four waves in order; a segment's items in item order;
+ * the segments in segment order).  No atomics: bit-identical from run to run.
+ * spair_grad_norm_items (host only, touches no GPU): returns the number of work items of the segment table, and with items != NULL writes
+ *   items[3 k .. 3 k + 2] = {segment, lo, hi}, segments in order, pieces in order.  SPAIR_ERR_SHAPE for n <= 0, nseg outside
+ *   [1, SPAIR_GRAD_MAX_SEGMENTS], a NULL seg_lo / seg_hi, an empty, descending or overlapping segment, a segment past n.
+ * spair_grad_norm (two launches on `stream`): items_dev: that table on the device; partial: double[n_items] (one per item, written);
+ *   seg_sumsq: double[nseg] (the squared norm per segment, written); out: float[2] = {norm, scale}, norm = (float)sqrt(total) and
+ *   scale = fminf(1, max_norm / (norm + norm_eps)) in fp32 when max_norm > 0 and the norm is finite, else exactly 1; clip: int[2]
+ *   (caller-zeroed, accumulating) = {calls with scale < 1, calls with a non-finite norm}.  max_norm <= 0: measure only.  Nothing is
+ *   written to grads.  SPAIR_ERR_SHAPE before any launch for a NULL pointer, n_items < nseg or >= 2^31, nseg outside
+ *   [1, SPAIR_GRAD_MAX_SEGMENTS], norm_eps < 0 or NaN, a NaN max_norm.  The table is trusted (it is spair_grad_norm_items' output).
+ * spair_adam_clipped: spair_adam_guarded on gradients scaled by norm_out[1] (spair_grad_norm's out, read on the device): gi = g[i] * scale
+ *   in place of g[i], in the per-element guard as well; grads is NOT written.  A non-finite norm_out[0] leaves the whole step out --
+ *   parameters and moments untouched, counters untouched (clip[1] counted it).  With scale == 1 the result is bit-identical to
+ *   spair_adam_guarded's.  SPAIR_ERR_SHAPE for n <= 0, step < 1, a NULL params / grads / exp_avg / exp_avg_sq / counters / norm_out. */
+#define SPAIR_GRAD_CHUNK 4096
+#define SPAIR_GRAD_MAX_SEGMENTS 4096
+int spair_grad_chunk(void);
+long long spair_grad_norm_items(const int64_t* seg_lo, const int64_t* seg_hi, int nseg, int64_t n, int64_t* items);
+int spair_grad_norm(const float* grads, const int64_t* items_dev, long long n_items, int nseg, double* partial, double* seg_sumsq,
+                    float* out, float max_norm, float norm_eps, int* clip, void* stream);
+int spair_adam_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
+                       float eps, int step, const int* skip, int* counters, const float* norm_out, void* stream);
 #ifdef __cplusplus
 }
 #endif

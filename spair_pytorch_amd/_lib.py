@@ -83,6 +83,7 @@ def lib():
         _declare_prior(h)
         _declare_evaluate(h)
         _declare_segmentation(h)
+        _declare_gradnorm(h)
         _lib = h
     return _lib
 
@@ -134,6 +135,19 @@ def _declare_segmentation(h):
     h.spair_scenes_generate_masks.argtypes = [ctypes.c_uint64, ll, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
     h.spair_segmentation.argtypes = [vp, vp, i, ll, i, i, vp, vp, vp, vp, vp]
     for fn in (h.spair_scenes_generate_masks, h.spair_segmentation):
+        fn.restype = i
+
+
+def _declare_gradnorm(h):
+    """Argument lists of the gradient-norm and clipped-Adam entry points (include/spair_hip.h, "gradient norm and clipping"): floats by
+    value, 64-bit counts."""
+    vp, i, f, ll, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong, ctypes.c_int64
+    h.spair_grad_chunk.argtypes = []
+    h.spair_grad_norm_items.argtypes = [vp, vp, i, i64, vp]
+    h.spair_grad_norm_items.restype = ll
+    h.spair_grad_norm.argtypes = [vp, vp, ll, i, vp, vp, vp, f, f, vp, vp]
+    h.spair_adam_clipped.argtypes = [vp, vp, vp, vp, i64, f, f, f, f, i, vp, vp, vp, vp]
+    for fn in (h.spair_grad_chunk, h.spair_grad_norm, h.spair_adam_clipped):
         fn.restype = i
 
 

@@ -16,6 +16,10 @@ element.  ``allreduce_gradients(model)`` makes a communication stream wait on ea
 that range's all-reduce there, so the decoder's 1.7 MB travel while the chain and the backbone
 backward still compute; Adam (on the caller's stream) waits on the last collective.  The reference
 has no counterpart (train.py:27-30 is single-device).
+
+Gradient clipping (``FusedAdam(max_grad_norm=...)``, ``optim.clip_grad_norm_``) belongs after ``allreduce_gradients``:
+``FusedAdam.step()`` is already ordered behind the collectives on the caller's stream, and the norm is then that of
+the summed global gradient, the same on every rank.
 """
 import ctypes
 
