@@ -91,7 +91,11 @@ typedef struct SpairStep {
      * spair/debug_tools.py:245-271, called at models.py:65,108,245).  spair_forward's loss kernel evaluates
      *   bits = 1 * (a band-split hand-off of the per-cell chain ever timed out on this workspace) | 2 * (a loss term of THIS forward is NaN / inf)
      * and, where the pointers are non-null, writes
-     *   status[0] |= bits (sticky), status[1] = bits (this step; spair_adam_guarded's skip word)   -- two ints in device memory, caller-owned;
+     *   status[0] |= bits (sticky)   -- two ints in device memory, caller-owned;
+     *   status[1] |= bits, only with train != 0   -- the word of the OPTIMIZER step (spair_adam_guarded's skip word): every train forward
+     *   since it was last cleared has ORed into it (micro-batches of one accumulated step), a forward with train == 0 leaves it alone (an
+     *   evaluation between backward and optimizer step changes nothing).  Whoever applies the step clears it afterwards (FusedAdam.step
+     *   does; hipMemsetAsync of the one int behind spair_adam_guarded in a C caller);
      *   *status_host = bits, only when bits != 0   -- one int of host memory the device can write (spair_host_word_alloc), so that the
      *   caller can poll it with a plain load at any later point (a normal step never touches it).  Both may be NULL. */
     int* status;
@@ -172,6 +176,11 @@ int spair_adam(float* params, const float* grads, float* exp_avg, float* exp_avg
  * synchronises anyway).  skip may be NULL (element guard only). */
 int spair_adam_guarded(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                        float beta1, float beta2, float eps, int step, const int* skip, int* counters, void* stream);
+/* Data-parallel replicas take ONE skip decision: exchange SpairStep.status[1] between the gradient all-reduce and the optimizer step.
+ * phase 0: xchg[0..1] = bits 0 and 1 of status[1] as 0 / 1 -- all-reduce the two ints with MAX -- phase 1: status[1] = the combined bits
+ * and, if any, status[0] |= them | 4 * (a bit this rank had not set itself: "flagged on another rank") and *status_host = status[0]
+ * (status_host may be NULL).  `xchg`: two device ints, caller-owned.  One single-thread kernel per phase on `stream`; no synchronisation. */
+int spair_status_exchange(int* status, int* xchg, int* status_host, int phase, void* stream);
 /* One int of host memory that kernels can store to (hipHostMalloc, mapped + coherent), zero-initialised: SpairStep.status_host. */
 int spair_host_word_alloc(int** out);
 int spair_host_word_free(int* word);

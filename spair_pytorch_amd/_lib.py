@@ -149,6 +149,8 @@ def _declare_gradnorm(h):
     h.spair_adam_clipped.argtypes = [vp, vp, vp, vp, i64, f, f, f, f, i, vp, vp, vp, vp]
     for fn in (h.spair_grad_chunk, h.spair_grad_norm, h.spair_adam_clipped):
         fn.restype = i
+    h.spair_status_exchange.argtypes = [vp, vp, vp, i, vp]
+    h.spair_status_exchange.restype = i
 
 
 def check(rc, what):

@@ -1268,7 +1268,7 @@ extern "C" int spair_forward(const SpairDims* d, const SpairStep* st, const Spai
     TRY(loss_finalize(c.w.bce_partial, render_num_blocks(d->B, d->I, d->Iw), c.w.kl_partial, loss_gauss_kl_blocks(L), c.w.klp, d->B,
                       st->kl_scale, d->vae_beta, io->loss_out,
                       c.use_chain && c.w.chain_sync ? c.w.chain_sync + CHAIN_SYNC_STICKY(d->B, chain_bands(*d)) : nullptr, st->status,
-                      st->status_host, c.s));
+                      st->status_host, st->train != 0, c.s));
     return SPAIR_OK;
 }
 

@@ -194,7 +194,7 @@ __global__ __launch_bounds__(256) void k_gauss_kl(CellLayout L, CellBufs P, Cell
 __global__ __launch_bounds__(256) void k_loss_finalize(const float* __restrict__ bce_partial, int n_bce, const float* __restrict__ kl_partial,
                                                        int n_kl, const float* __restrict__ klp, int B, float kl_scale, float beta,
                                                        float* __restrict__ loss_out, const int* __restrict__ failed,
-                                                       int* __restrict__ status, int* __restrict__ status_host) {
+                                                       int* __restrict__ status, int* __restrict__ status_host, int train) {
     // all eight sums in one pass: every load of a thread is issued before the first add, one LDS reduction for the lot
     // (eight block reductions in sequence, each behind its own dependent loads, took 23 us between the renderer's two passes)
     __shared__ float red[4][8];
@@ -243,7 +243,9 @@ __global__ __launch_bounds__(256) void k_loss_finalize(const float* __restrict__
         // SpairStep.status / status_host (include/spair_hip.h): a failed or non-finite step announces itself without a host synchronisation
         // (every loss term feeds `total`, so one test covers the nine)
         const int bits = timed_out | (fabsf(total) <= 3.402823466e38f ? 0 : 2);
-        if (status) { status[1] = bits; if (bits) status[0] |= bits; }
+        // status[1] belongs to the optimizer step, not to this forward: a train forward ORs into it (micro-batches accumulate; whoever
+        // applies the step clears it), any other forward leaves it alone (an evaluation between backward and step changes nothing)
+        if (status && bits) { status[0] |= bits; if (train) status[1] |= bits; }
         if (status_host && bits) *(volatile int*)status_host = bits;
     }
 }
@@ -273,9 +275,9 @@ int loss_gauss_kl(const CellLayout& L, const CellBufs& P, const CellHyper& H, fl
     return SPAIR_OK;
 }
 int loss_finalize(const float* bce_partial, int n_bce, const float* kl_partial, int n_kl, const float* klp, int B, float kl_scale,
-                  float beta, float* loss_out, const int* failed, int* status, int* status_host, hipStream_t s) {
+                  float beta, float* loss_out, const int* failed, int* status, int* status_host, int train, hipStream_t s) {
     hipLaunchKernelGGL(k_loss_finalize, dim3(1), dim3(256), 0, s, bce_partial, n_bce, kl_partial, n_kl, klp, B, kl_scale, beta, loss_out, failed,
-                       status, status_host);
+                       status, status_host, train);
     SPAIR_CHECK_LAUNCH();
     return SPAIR_OK;
 }

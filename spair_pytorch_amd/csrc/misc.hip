@@ -63,6 +63,31 @@ extern "C" int spair_adam_guarded(float* params, const float* grads, float* exp_
     return SPAIR_OK;
 }
 
+// Data-parallel exchange of the step word (include/spair_hip.h): one thread each.  pack: xchg = {bit 0, bit 1} of status[1] as 0 / 1, the form
+// a MAX all-reduce combines per bit.  merge: status[1] = the combined bits; what this rank did not see itself is marked with bit 4 in the
+// sticky word and the host word, so that this rank too is loud once the step has completed.
+__global__ void k_status_pack(const int* __restrict__ status, int* __restrict__ xchg) {
+    const int w = status[1];
+    xchg[0] = w & 1;
+    xchg[1] = (w >> 1) & 1;
+}
+__global__ void k_status_merge(int* __restrict__ status, const int* __restrict__ xchg, int* __restrict__ status_host) {
+    const int all = (xchg[0] ? 1 : 0) | (xchg[1] ? 2 : 0);
+    if (!all) return;
+    const int remote = all & ~status[1];
+    const int sticky = status[0] | all | (remote ? 4 : 0);
+    status[1] = all;
+    status[0] = sticky;
+    if (status_host) *(volatile int*)status_host = sticky;
+}
+extern "C" int spair_status_exchange(int* status, int* xchg, int* status_host, int phase, void* stream) {
+    if (!status || !xchg || (phase != 0 && phase != 1)) return SPAIR_ERR_SHAPE;
+    if (phase == 0) hipLaunchKernelGGL(k_status_pack, dim3(1), dim3(1), 0, (hipStream_t)stream, status, xchg);
+    else hipLaunchKernelGGL(k_status_merge, dim3(1), dim3(1), 0, (hipStream_t)stream, status, xchg, status_host);
+    SPAIR_CHECK_LAUNCH();
+    return SPAIR_OK;
+}
+
 extern "C" int spair_host_word_alloc(int** out) {
     if (!out) return SPAIR_ERR_SHAPE;
     void* p = nullptr;

@@ -17,6 +17,13 @@ that range's all-reduce there, so the decoder's 1.7 MB travel while the chain an
 backward still compute; Adam (on the caller's stream) waits on the last collective.  The reference
 has no counterpart (train.py:27-30 is single-device).
 
+A failed step (optim.py): ``FusedAdam.step()`` leaves out a step whose loss was flagged non-finite or timed out, and it reads a word in
+this rank's own memory.  ``allreduce_gradients(model)`` therefore exchanges that word too -- two ints, a MAX all-reduce beside the first
+gradient bucket (spair_status_exchange) -- so that every rank takes the SAME decision: a step any rank flagged is left out on all of
+them, parameters, moments and ``skipped()[0]`` stay equal across replicas, and every rank is loud afterwards (``check_step_status()``
+and the next ``forward()`` raise everywhere, a rank flagged only through another one says so: bit 4), so no rank walks on into a
+collective the flagged rank never reaches.  The flat-tensor form knows no model: there the caller owns that exchange.
+
 Gradient clipping (``FusedAdam(max_grad_norm=...)``, ``optim.clip_grad_norm_``) belongs after ``allreduce_gradients``:
 ``FusedAdam.step()`` is already ordered behind the collectives on the caller's stream, and the norm is then that of
 the summed global gradient, the same on every rank.
@@ -69,9 +76,27 @@ def broadcast_parameters(flat_params, src=0):
     dist.broadcast(flat_params, src)
 
 
+def _exchange_status(model, phase):
+    """spair_status_exchange on the current stream: phase 0 packs the model's step word into its two exchange ints, phase 1 merges the
+    all-reduced ints back into the step word, the sticky word and the host word.  No allocation after the first call."""
+    status = getattr(model, "_status_dev", None)
+    if status is None:
+        return None
+    x = getattr(model, "_status_xchg", None)
+    if x is None or x.device != status.device:
+        x = model._status_xchg = torch.zeros(2, dtype=torch.int32, device=status.device)
+    host = ctypes.cast(model._status_host, ctypes.c_void_p) if model._status_host is not None else ctypes.c_void_p(0)
+    L.check(L.lib().spair_status_exchange(L.ptr(status), L.ptr(x), host, int(phase), L.stream()), "spair_status_exchange")
+    return x
+
+
 def allreduce_gradients(target):
     """SUM (not mean) over ranks, in place.  ``target`` is a model prepared by ``attach`` (bucketed, overlapped
-    with the tail of its backward) or a flat gradient tensor (one bucket, on the current stream)."""
+    with the tail of its backward) or a flat gradient tensor (one bucket, on the current stream).
+
+    With a model, the word ``FusedAdam.step()`` reads as its skip flag is exchanged as well (MAX over ranks, one collective of two
+    ints): after this call every rank leaves the step out if any rank flagged it.  With a flat tensor nothing is known of a model:
+    the caller owns that exchange (or every rank may take its own decision and the replicas diverge)."""
     if isinstance(target, torch.Tensor):
         dist.all_reduce(target, op=dist.ReduceOp.SUM)
         return
@@ -79,10 +104,15 @@ def allreduce_gradients(target):
     flat = model.flat_gradients()
     gb = getattr(model, "_grad_buckets", None)
     if gb is None or not gb.pending:
+        xchg = _exchange_status(model, 0)
         dist.all_reduce(flat, op=dist.ReduceOp.SUM)
+        if xchg is not None:
+            dist.all_reduce(xchg, op=dist.ReduceOp.MAX)
+            _exchange_status(model, 1)
         return
     gb.pending = False
     works = []
+    xchg = None
     with torch.cuda.stream(gb.comm):
         for i, (ev, (lo, hi)) in enumerate(zip(gb.events, gb.ranges)):
             gb.comm.wait_event(ev)                       # this range's gradients are final
@@ -93,9 +123,17 @@ def allreduce_gradients(target):
                 w.wait()                                 # the communication stream waits for the collective: `t_done` is its completion
                 gb.t_done[i].record(gb.comm)
             works.append(w)
+            if i == 0:
+                # the step word was final with the forward's loss kernel, long before the first range: its two ints travel behind the
+                # first bucket (after that bucket's timing marks, which stay the gradient collective's own)
+                xchg = _exchange_status(model, 0)
+                if xchg is not None:
+                    works.append(dist.all_reduce(xchg, op=dist.ReduceOp.MAX, async_op=True))
     for w in works:
         w.wait()                                         # the CALLER's stream (Adam) waits for the collectives
     torch.cuda.current_stream().wait_stream(gb.comm)
+    if xchg is not None:
+        _exchange_status(model, 1)                       # on the caller's stream, in front of Adam
 
 
 def bucket_timings(model, backward_end=None):

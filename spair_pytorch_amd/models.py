@@ -187,6 +187,8 @@ class EvalResult:
 
 class _NullWriter:
     def __getattr__(self, name):
+        if name.startswith("__"):         # copy / pickle probe for __deepcopy__, __getstate__, ...: a writer has none of them
+            raise AttributeError(name)
         return lambda *a, **k: None
 
 
@@ -379,6 +381,26 @@ class SPAIR(nn.Module):
             L.check(lib.spair_host_word_alloc(ctypes.byref(word)), "spair_host_word_alloc")
             self._status_host = word
             weakref.finalize(self, lib.spair_host_word_free, word)
+
+    # ---- copies: copy.deepcopy(model), pickle, torch.save(model) -------------------------------------------
+    # what belongs to THIS object's device state and holds raw pointers, events or a multi-GB workspace
+    _PER_INSTANCE = ("_flat", "_flat_grad", "_slices", "_params_by_key", "_anchor", "_engines", "_last", "_loss_terms", "_status_dev",
+                     "_status_host", "_status_xchg", "_grad_buckets", "_grad_norm_tables", "dist_param", "dist")
+
+    def __getstate__(self):
+        """A copy (an EMA or evaluation model, a pickled checkpoint) takes the parameters, buffers and settings; it gets its OWN flat
+        buffers, gradient buffer, engines and status words, built on first use as for a new model -- a failed step on one of the two
+        never makes the other raise.  ``ddp.attach`` is per object: attach the copy if it is to train."""
+        state = dict(self.__dict__)
+        for k in self._PER_INSTANCE:
+            state.pop(k, None)
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self._flat = self._flat_grad = self._anchor = self._loss_terms = self._last = None
+        self._status_dev = self._status_host = self._grad_buckets = None
+        self._engines, self.dist_param, self.dist = {}, {}, {}
 
     def _apply(self, fn, recurse=True):
         # .to(device)/.cuda()/.float(): let nn.Module move the tensors, then re-flatten on the new device
@@ -607,8 +629,9 @@ class SPAIR(nn.Module):
         ``owner_weight`` is the raw maximum either way.
 
         Like any forward it overwrites the workspace of that batch size: ``backward()`` of an earlier forward of the same batch size
-        raises afterwards (the generation check).  And as any ``no_grad`` forward, it rewrites the step-status word ``FusedAdam`` reads as
-        its skip flag: do not call it between ``backward()`` and ``FusedAdam.step()``."""
+        raises afterwards (the generation check).  As any ``no_grad`` forward it leaves the word ``FusedAdam.step()`` reads as its skip
+        flag alone: it may be called anywhere, between ``backward()`` and ``step()`` too (a non-finite loss of its own still sets the
+        sticky word and the host word, as ``forward`` does)."""
         self._ensure_ready()
         if not x.is_cuda:
             raise L.SpairHipError("input must be on the MI355X (got %s); there is no CPU path" % x.device)
@@ -794,8 +817,8 @@ class SPAIR(nn.Module):
         ``forward`` does (``torch.manual_seed`` controls it), then behaves as ``seed=int``.
 
         Like ``parse`` it overwrites the workspace of that batch size: ``backward()`` of an earlier forward of the same batch size raises
-        afterwards (the generation check).  And as any ``no_grad`` forward it rewrites the step-status word ``FusedAdam`` reads as its
-        skip flag: it must not be called between ``backward()`` and ``FusedAdam.step()``.  No gradients flow through it."""
+        afterwards (the generation check).  As any ``no_grad`` forward it leaves the word ``FusedAdam.step()`` reads as its skip flag
+        alone: it may run between ``backward()`` and ``FusedAdam.step()``.  No gradients flow through it."""
         self._ensure_ready()
         if not x.is_cuda:
             raise L.SpairHipError("input must be on the MI355X (got %s); there is no CPU path" % x.device)
@@ -890,10 +913,14 @@ class SPAIR(nn.Module):
         if bits & 1:
             what.append("a band-split hand-off of the per-cell chain timed out (preempted / oversubscribed GPU?): the results of that "
                         "workspace are not to be used -- restart the process, do not retry in place")
+        if bits & 4:
+            what.append("flagged on another rank: ddp.allreduce_gradients exchanged the step word and every replica left the step out "
+                        "(the bits above that this rank did not see itself are the other rank's)")
         return "; ".join(what) or "ok"
 
     def step_status(self):
-        """Bits of every forward of this model so far (sticky): 1 = a band-split hand-off timed out, 2 = a loss term was non-finite; 0 = clean.
+        """Bits of every forward of this model so far (sticky): 1 = a band-split hand-off timed out, 2 = a loss term was non-finite,
+        4 = another rank flagged a step (ddp.allreduce_gradients; with the other rank's bits); 0 = clean.
         SYNCHRONISES -- call it where the host waits anyway (after ``loss.item()``, at the end of an epoch).  The same word is also
         kept in host memory the loss kernel writes to: ``forward()`` looks at it (a host load, no synchronisation) and raises once a
         failed step has completed, unless ``raise_on_nonfinite`` is off.  ``FusedAdam`` leaves a flagged step out (no NaN parameters)."""

@@ -1,9 +1,19 @@
 """Fused Adam (K9) over the model's flat parameter / gradient buffers: one launch per step.
 Numerically torch.optim.Adam(lr) with its defaults (train.py:44).
 
-Guarded (spair_adam_guarded): a step whose forward flagged a non-finite loss is left out whole -- parameters and moments untouched -- and
-an element whose gradient is NaN / inf on its own; ``lr * NaN`` never reaches a parameter.  ``skipped()`` reports both (synchronises),
-``model.forward`` raises on the flag by itself once the failed step has completed (models.py).
+Guarded (spair_adam_guarded).  The contract of a failed step:
+  * ``step()`` leaves the step out whole -- parameters and both moments untouched -- if ANY grad-enabled forward of the model since the
+    previous ``step()`` flagged a non-finite or timed-out loss: the loss kernel ORs into one device word per optimizer step
+    (``SpairStep.status[1]``), so a flagged micro-batch under gradient accumulation holds whatever the later ones did, and ``step()``
+    clears the word behind the Adam kernel.  ``skipped()[0]`` counts such a step once.
+  * no ``no_grad`` forward, ``parse``, ``evaluate``, ``compose`` or ``generate`` changes that word, wherever it falls between
+    ``backward()`` and ``step()``.
+  * data-parallel replicas take the same decision: ``ddp.allreduce_gradients(model)`` exchanges the word, and a step any rank flagged
+    is left out on all of them (ddp.py).
+  * an element whose gradient is NaN / inf is left out on its own; ``lr * NaN`` never reaches a parameter.
+  * a single-process step pays one word-sized device fill for this: no synchronisation, no allocation, and the whole step stays
+    capturable in a HIP graph.
+``skipped()`` reports both (synchronises), ``model.forward`` raises on the flag by itself once the failed step has completed (models.py).
 
 Clipped (``max_grad_norm``; spair_grad_norm + spair_adam_clipped, csrc/gradnorm.hip): the gradients are scaled by
 ``min(1, max_grad_norm / (norm + norm_eps))``, norm = the global L2 norm of the flat gradient buffer -- torch.nn.utils.clip_grad_norm_ in
@@ -175,7 +185,7 @@ class FusedAdam:
         self.model._bind_grads()
         self.step_count += 1
         status = getattr(self.model, "_status_dev", None)
-        skip = ctypes.c_void_p(status.data_ptr() + 4) if status is not None else ctypes.c_void_p(0)       # this step's bits
+        skip = ctypes.c_void_p(status.data_ptr() + 4) if status is not None else ctypes.c_void_p(0)       # this optimizer step's bits
         if self.max_grad_norm is not None:
             return self._step_clipped(flat, skip)
         L.check(L.lib().spair_adam_guarded(L.ptr(flat), L.ptr(self.model.flat_gradients()), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
@@ -183,6 +193,14 @@ class FusedAdam:
                                            ctypes.c_float(self.betas[1]), ctypes.c_float(self.eps), int(self.step_count), skip,
                                            L.ptr(self._counters), L.stream()),
                 "spair_adam_guarded")
+        self._clear_step_word(status)
+
+    @staticmethod
+    def _clear_step_word(status):
+        """The word belongs to the optimizer step that has just read it: the next step starts from a clean one (a fill of one int on the
+        caller's stream, behind the Adam kernel; the sticky word and the host word keep the failure loud)."""
+        if status is not None:
+            status[1].zero_()
 
     def _step_clipped(self, flat, skip):
         self._gn.run(self.max_grad_norm, self.norm_eps)
@@ -191,6 +209,7 @@ class FusedAdam:
                                            ctypes.c_float(self.betas[1]), ctypes.c_float(self.eps), int(self.step_count), skip,
                                            L.ptr(self._counters), L.ptr(self._gn.out), L.stream()),
                 "spair_adam_clipped")
+        self._clear_step_word(getattr(self.model, "_status_dev", None))
         self._clipped_once = True
 
     @property
