@@ -565,6 +565,45 @@ int spair_scenes_generate_masks(uint64_t seed, long long first, int B, int I, in
  * contingency or scores. */
 int spair_segmentation(const int* pred, const int* truth, int B, long long HW, int NP, int K, int* contingency, float* scores,
                        int* match, float* match_iou, void* stream);
+/* ---- detection metrics (csrc/detection.hip): predicted boxes with scores against the true boxes of each image, on the device: ranked,
+ * matched greedily one-to-one at every IoU threshold, and the precision / recall curve pooled over all the images fed.
+ * Per image b: predictions n = 0 .. N-1 with boxes [B][N][4] = (x0, y0, x1, y1) in pixels (true corners, as parse_boxes gives them --
+ *   not the top-left reading of spair_metrics) and scores [B][N]; truths j = 0 .. K-1 with bbox [B][K][4] = (x, y, w, h) in pixels (the
+ *   scene generator's format; corners x, y, x + w, y + h, each sum rounded once), of which the first cnt[b] = clamp(count[b], 0, K)
+ *   are real; thresholds [T] in fp32.  1 <= N <= 1024, 1 <= K <= 32, 1 <= T <= 16, 1 <= max_det <= N, min_score finite.
+ * IoU of boxes a, b, in fp32, one rounding per operation and no contraction:
+ *     iw = max(min(ax1, bx1) - max(ax0, bx0), 0), ih likewise;  inter = iw * ih;
+ *     ua = (ax1 - ax0) * (ay1 - ay0), ub likewise;  un = (ua + ub) - inter;  iou = un > 0 ? inter / un : 0;
+ *   and +0 where that is not above 0 (an empty intersection, a NaN) or where any of the eight coordinates is NaN or infinite.
+ * Live: a prediction whose score is no NaN and >= min_score; n_pred[b] = the number of live predictions, before any cap.
+ * Ranked list: the live predictions by score descending (-0 = +0), equal scores by lower n first; only the first
+ *   kept = min(n_pred, max_det) enter the matching (COCO's maxDets).
+ * Matching, for every threshold t on its own: walk the ranked list in order; among the real truths not yet taken at t choose the one
+ *   with the largest IoU, on equal IoU the lowest j; if that IoU >= thresholds[t] (an fp32 compare) the prediction is a true positive at t
+ *   and takes the truth, otherwise (or with no truth left) a false positive at t.  Bit t of the prediction's tp word is the outcome.
+ * spair_det_match (one launch on `stream`) writes, with a fixed stride of max_det slots per image at the caller's row pointers,
+ *   score [B][max_det], tp [B][max_det], order [B][max_det] (the prediction's index n) in ranked order, dead slots -inf / 0 / -1;
+ *   n_pred [B], n_truth [B] (= cnt); iou [B][N][K] (may be NULL: not touched; else written whole, all K truth slots as given); and ADDS
+ *   to counters[SPAIR_DET_COUNTERS] (64-bit, caller-zeroed, integer atomics: exact and order-independent): 0 sum of cnt, 1 sum of kept
+ *   (the records), 2 images with n_pred == cnt, 3 sum of |n_pred - cnt|, 4 sum of n_pred - cnt, 5 images, 6 .. 7 unused,
+ *   8 + t the true positives at threshold t.
+ * Pooled curve: the records (score, tp word) in insertion order -- image by image as fed, ranked order inside an image -- sorted by score
+ *   descending, STABLY (the caller's sort; dead slots, -inf, come last).  For threshold t, over the M = counters[1] records:
+ *     TP_i = records 0 .. i with bit t set, prec_i = TP_i / (i + 1), NT = counters[0];
+ *     AP_t = (1 / NT) sum over the records i with bit t set of max_{k >= i} prec_k (the area under the precision envelope, all points);
+ *     NaN if NT = 0, 0 without a record;  recall_t = TP_last / NT (NaN if NT = 0);  precision_t = TP_last / M (NaN if M = 0).
+ *   Counts are exact integers; the divisions and the sum are float64, the sum in an order fixed by M alone.
+ * spair_det_ap (one launch on `stream`, no atomics: bit-identical from run to run): tp_sorted [M_slots] the tp words in sorted order,
+ *   counters the block above (read on the device: counters[1] is clamped to M_slots), out double [3][T] = AP, recall, precision.
+ * Count statistics over the images fed, from the integer sums: count_accuracy = counters[2] / counters[5], count_mae = counters[3] /
+ *   counters[5], count_bias = counters[4] / counters[5].
+ * Both: no allocation, no host synchronisation.  SPAIR_ERR_SHAPE before any launch for B < 1, N, K, T or max_det outside the limits
+ *   above, a NaN or infinite min_score, M_slots outside [1, 2^31 - 1], a NULL pointer other than iou. */
+#define SPAIR_DET_COUNTERS 24
+int spair_det_match(const float* boxes, const float* scores, const float* bbox, const int* count, const float* thresholds, int B, int N,
+                    int K, int T, float min_score, int max_det, float* score, int* tp, int* order, int* n_pred, int* n_truth,
+                    long long* counters, float* iou, void* stream);
+int spair_det_ap(const int* tp_sorted, long long M_slots, int T, const long long* counters, double* out, void* stream);
 /* ---- gradient norm and clipping by global L2 norm (csrc/gradnorm.hip; torch.nn.utils.clip_grad_norm_ in front of the Adam of
  * train.py:44, which the reference itself never calls).  The norm is taken over SEGMENTS of the flat gradient buffer -- nseg ascending,
  * non-overlapping, non-empty element ranges [seg_lo[s], seg_hi[s]), gaps allowed and never read -- cut into WORK ITEMS (segment, lo, hi) of at

@@ -7,7 +7,7 @@ there is no PyTorch/CPU fallback.
 from . import config  # noqa: F401
 
 __all__ = ["config", "SPAIR", "ParseResult", "ComposeResult", "GenerateResult", "EvalResult", "parse_boxes",
-           "segmentation", "SegmentationResult"]
+           "segmentation", "SegmentationResult", "DetectionAP", "DetectionBatch", "DetectionResult", "detection_ap"]
 
 
 def __getattr__(name):
@@ -18,4 +18,7 @@ def __getattr__(name):
     if name in ("segmentation", "SegmentationResult"):
         from . import metric
         return getattr(metric, name)
+    if name in ("DetectionAP", "DetectionBatch", "DetectionResult", "detection_ap"):
+        from . import detection
+        return getattr(detection, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

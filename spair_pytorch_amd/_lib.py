@@ -83,6 +83,7 @@ def lib():
         _declare_prior(h)
         _declare_evaluate(h)
         _declare_segmentation(h)
+        _declare_detection(h)
         _declare_gradnorm(h)
         _lib = h
     return _lib
@@ -135,6 +136,15 @@ def _declare_segmentation(h):
     h.spair_scenes_generate_masks.argtypes = [ctypes.c_uint64, ll, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
     h.spair_segmentation.argtypes = [vp, vp, i, ll, i, i, vp, vp, vp, vp, vp]
     for fn in (h.spair_scenes_generate_masks, h.spair_segmentation):
+        fn.restype = i
+
+
+def _declare_detection(h):
+    """Argument lists of the detection-metric entry points (include/spair_hip.h, "detection metrics"): a float by value, a 64-bit count."""
+    vp, i, f, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong
+    h.spair_det_match.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, f, i, vp, vp, vp, vp, vp, vp, vp, vp]
+    h.spair_det_ap.argtypes = [vp, ll, i, vp, vp, vp]
+    for fn in (h.spair_det_match, h.spair_det_ap):
         fn.restype = i
 
 
